@@ -18,6 +18,11 @@ Workload: the 100 002-atom water box with 1 ensemble member — the configuratio
 (examples/benchmark/README.md:78-81).  N > 1: the SAME box split into N bricks (strong scaling), as LAMMPS' spatial
 decomposition does for the reference (examples/benchmark/submit_scaling.py:13-21).
 
+A plain run times only the headline: set-up, W warm-up steps, the K timed steps, the result line.  `--full` adds everything
+else the bench measures and checks (hot path alone, full-width AEV pass, parity against the CPU oracle, CPU baseline,
+roofline, re-neighbouring cost, adapter path, reduced-precision pass, secondary configurations).  `--dump-outputs DIR`
+writes what the last timed step left to its caller as DIR/<name>.npy (see write_outputs).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -71,7 +76,41 @@ def parse_args(argv=None):
                     "ghosts (ani_step_begin / _ghosts_ready / _finish); also ANI_MD_OVERLAP=1")
     ap.add_argument("--no-md", action="store_true", help="hot path only: `value` is then the static-position rate (development runs)")
     ap.add_argument("--repulsion", action="store_true", help="model with the optional pairwise repulsion block (not the headline configuration)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements and checks (hot path, parity, CPU baseline, "
+                    "roofline, re-neighbouring cost, adapter path, other precisions and configurations); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 2024
+
+
+def write_outputs(dirname, per_atom, totals, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 kept, anything else as float64.  per_atom: arrays whose rows are
+    the atoms in global order; totals: whole-system values.  Should the files pass `limit` bytes, the per-atom arrays keep one
+    fixed, seeded sample of their rows (ascending, the same rows in every array), as many as fit.  Returns the names written."""
+    import numpy as np
+
+    def as_float(a):
+        a = np.asarray(a)
+        return np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+
+    per_atom = {k: as_float(v) for k, v in per_atom.items()}
+    totals = {k: np.atleast_1d(as_float(v)) for k, v in totals.items()}
+    header = 1024   # bound on one .npy header
+    fixed = sum(a.nbytes + header for a in totals.values()) + header * len(per_atom)
+    if per_atom and fixed + sum(a.nbytes for a in per_atom.values()) > limit:
+        n = len(next(iter(per_atom.values())))
+        row_bytes = sum(a.nbytes // max(n, 1) for a in per_atom.values())
+        keep = max(min((limit - fixed) // max(row_bytes, 1), n), 1)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        per_atom = {k: a[rows] for k, a in per_atom.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in {**per_atom, **totals}.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted({**per_atom, **totals})
 
 
 def launch_ranks(args):
@@ -282,6 +321,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    def gather_outputs(tag, per_atom, totals):
+        """--dump-outputs: the per-atom arrays of every rank with their rows in global atom order (tag) and the totals summed
+        over ranks, on rank 0 (None on the others); a collective, every rank calls it"""
+        tag = np.asarray(tag, dtype=np.int64)
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, (tag, per_atom, totals))
+            tag = np.concatenate([p[0] for p in parts])
+            per_atom = {k: np.concatenate([p[1][k] for p in parts]) for k in per_atom}
+            totals = {k: sum(p[2][k] for p in parts) for k in totals}
+        if rank != 0:
+            return None
+        order = np.argsort(tag, kind="stable")
+        return {k: v[order] for k, v in per_atom.items()}, totals
+
     class Workload:
         """One box on this rank for the hot-path pass: decomposition, device tensors, library handle, ghost exchange."""
 
@@ -351,11 +405,14 @@ def main():
         def close(self):
             self.ani.close()
 
-    def md_pass(system, steps, warmup, arith=None, with_parity=False, measure_rebuilds=True):
+    def md_pass(system, steps, warmup, arith=None, with_parity=False, measure_rebuilds=True, headline=False):
         """The reference benchmark's timestep loop on the device, W untimed + K timed steps.  arith: mlp_arith of the pass
         (None = the library default, the exact split).  After the timed region the loop keeps running, untimed, in blocks of
         `every` steps (the cadence of the displacement check) until it has seen re-neighbourings, so that the cost of a
-        rebuild step and the interval between rebuilds are measured whatever K was."""
+        rebuild step and the interval between rebuilds are measured whatever K was.  measure_rebuilds False: no such
+        continuation, except that the headline pass (headline True) still takes the longer window when its K steps held no
+        re-neighbouring, which the headline then needs.  With --dump-outputs the headline pass also returns the state its
+        last timed step left (gather_outputs), else None."""
         path = f"/tmp/bench_ani2x_m{args.models}_md_r{rank}.anim"
         # The seeded weights have no minimum at the start structure, so the output layer is scaled to keep the surface
         # within a few kT (same shapes, same arithmetic, a liquid that stays a liquid at 300 K)
@@ -388,19 +445,23 @@ def main():
         parity = None
         if with_parity and world == 1:
             # the MD pass runs on its own model file (output layer scaled): its forces at the start structure against the
-            # oracle on that same file (owned atoms keep their order on one rank; ghost forces already folded by the loop)
-            from oracle import Oracle
-            ref = Oracle(path).compute(inp, radial_compat=(args.aev == "pyaev"))
-            fr = ref["force"][: inp.nlocal].copy()
-            np.add.at(fr, inp.owner_lidx, ref["force"][inp.nlocal:])
+            # oracle on that same file (owned atoms keep their order on one rank; ghost forces already folded by the loop).
+            # Without --full the oracle is skipped but the forces are evaluated all the same: the thermostat noise drawn here
+            # comes before the velocities are, so the command follows one trajectory with or without --full
+            if args.full:
+                from oracle import Oracle
+                ref = Oracle(path).compute(inp, radial_compat=(args.aev == "pyaev"))
+                fr = ref["force"][: inp.nlocal].copy()
+                np.add.at(fr, inp.owner_lidx, ref["force"][inp.nlocal:])
             run._forces()                 # the pair style's forces alone (set-up had already added the thermostat's share)
-            f0 = run.f[: run.nlocal].cpu().numpy()
+            f0 = run.f[: run.nlocal].cpu().numpy() if args.full else None
             run._post_force()             # ... which is put back before the first step integrates
-            err = np.abs(f0 - fr)
-            parity = {"max_abs_force_err_kcal_mol_A": float(err.max()), "rms_force_err": float(np.sqrt((err ** 2).mean())),
-                      "max_abs_force": float(np.abs(fr).max()),
-                      "energy_err_kcal_mol": float(abs(run.potential_energy() - ref["energy"])),
-                      "what": f"forces of the MD pass's model (out_scale={MD_OUT_SCALE}) at the start structure vs oracle/ani_oracle.c on the same file"}
+            if args.full:
+                err = np.abs(f0 - fr)
+                parity = {"max_abs_force_err_kcal_mol_A": float(err.max()), "rms_force_err": float(np.sqrt((err ** 2).mean())),
+                          "max_abs_force": float(np.abs(fr).max()),
+                          "energy_err_kcal_mol": float(abs(run.potential_energy() - ref["energy"])),
+                          "what": f"forces of the MD pass's model (out_scale={MD_OUT_SCALE}) at the start structure vs oracle/ani_oracle.c on the same file"}
         run.create_velocities(300.0)
         # first-use costs belong to set-up, not to whichever step meets them first: the displacement check (a host round trip
         # every 10th step only) and the phase events are exercised here; the W warm-up steps follow
@@ -418,6 +479,15 @@ def main():
                 after_forces=lambda k: ani.phase_timing(0) if k % 4 == 0 else None)
         sync_all()
         dt = max_over_ranks(time.perf_counter() - t0)
+        dumped = None
+        if headline and args.dump_outputs:
+            # what `run K` leaves its caller: positions, velocities and forces (pair style + thermostat, as in LAMMPS' atom->f
+            # after post_force) of the owned atoms, and the pair style's energy of the last force evaluation
+            n = run.nlocal
+            dumped = gather_outputs(run.tag[:n].cpu().numpy(),
+                                    {"positions": run.x[:n].cpu().numpy(), "velocities": run.v[:n].cpu().numpy(),
+                                     "forces": run.f[:n].cpu().numpy()},
+                                    {"potential_energy": float(run.ev[0])})
         ph = ani.phase_times()
         ke = run.kinetic_energy()
         natoms_all = run._allreduce_sum(torch.tensor([float(run.nlocal)], dtype=torch.float64, device=dev))
@@ -430,7 +500,8 @@ def main():
                 "mlp_arith": arith if arith is not None else 1}
         if parity:
             info["parity_md_model"] = parity
-        if measure_rebuilds:
+        continued = measure_rebuilds or (headline and info["list_rebuilds"] == 0)
+        if continued:
             # untimed continuation, without a break in the loop: on until it has re-neighboured three times (at least 100
             # steps, at most 600).  Its rate is the loop's rate whatever K was; with the K-step window it also gives the cost
             # of a plain step and the surcharge of a re-neighbouring step (two windows, two unknowns).
@@ -445,6 +516,7 @@ def main():
             if r2 > 0:
                 info["amortised_ms_per_step"] = t_post / n_post * 1e3
                 info["rebuild_interval_steps"] = (steps + n_post) / (r1 + r2)
+        if measure_rebuilds:
             # cost of a re-neighbouring step, measured directly: single steps bracketed by synchronisations, alternately a
             # plain one and one forced to re-neighbour (both carry the same pipeline-refill bubble; their difference is the
             # surcharge of exchange + borders + device list + re-bucketing)
@@ -473,42 +545,54 @@ def main():
             t_sus = max_over_ranks(time.perf_counter() - t2)
             info["sustained_window"] = {"steps": n_sus, "list_rebuilds": run.nbuilds - nb1, "ms_per_step": t_sus / n_sus * 1e3,
                                         "ns_per_day": n_sus / t_sus * 0.0432, "wall_s": t_sus}
+        if continued:
             info["energy_finite"] = info["energy_finite"] and bool(np.isfinite(run.potential_energy()))
         view = ani.debug_view()
         ani.close()
         if native is not None:
             native.close()
-        return dt, ph, info, view.aev_active_length
+        return dt, ph, info, view.aev_active_length, dumped
 
     # ---- hot path on static positions (phase times for the secondary numbers, parity against the oracle) -------------
-    wl = Workload(args.atoms, args.models, repulsion=args.repulsion)
-    ani, inp, model, system = wl.ani, wl.inp, wl.model, wl.system
-    if args.dense_aev:
-        ani.set_option("prune_absent_species", 0)
-    dense_pass = None
-    if world == 1 and not args.dense_aev and not args.no_dense_pass:
-        # secondary number: the same workload with the full 1008-wide AEV rows (columns of absent species kept)
-        n2 = max(args.steps // 2, 1)
-        ani.set_option("prune_absent_species", 0)
-        dtd, phd = wl.timed_run(n2, args.warmup)
-        dense_pass = {"ms_per_step": dtd / n2 * 1e3, "value": n2 / dtd * 0.0432,
-                      "phase_ms": {k: phd[k] / max(phd["calls"], 1) for k in ("compact", "aev_fwd", "mlp", "aev_bwd")}}
-        fl = mlp_flops_per_step(model, np.bincount(system.types - 1, minlength=model.num_species))
-        dense_pass["mlp_algorithmic_fp32_tflops"] = fl / (dense_pass["phase_ms"]["mlp"] * 1e-3) / 1e12
-        dense_pass["mlp_frac_of_16bit_mfma_peak"] = 6.0 * dense_pass["mlp_algorithmic_fp32_tflops"] / PEAK_16BIT_MFMA_TFLOPS
-        ani.set_option("prune_absent_species", 1)
-    dt_hot, ph_hot = wl.timed_run(args.steps, args.warmup)
-    energy_local = float(wl.d_ev[0].item())
-    if not np.isfinite(energy_local) and not os.environ.get("ANI_BENCH_ALLOW_NAN"):   # the variable: timing-only ablation builds
-        raise SystemExit("non-finite energy: LDS neighbour capacity exceeded or numerical failure")
-    aev_cols = ani.debug_view().aev_active_length  # columns of the species present (1008 when all 7 occur)
-    mlp_kernel_name = ani.last_mlp_kernel()
+    # a plain run has it only when it is the headline (--no-md)
+    wl, dumped = None, None
+    if args.full or args.no_md:
+        wl = Workload(args.atoms, args.models, repulsion=args.repulsion)
+        ani, inp, model, system = wl.ani, wl.inp, wl.model, wl.system
+        if args.dense_aev:
+            ani.set_option("prune_absent_species", 0)
+        dense_pass = None
+        if args.full and world == 1 and not args.dense_aev and not args.no_dense_pass:
+            # secondary number: the same workload with the full 1008-wide AEV rows (columns of absent species kept)
+            n2 = max(args.steps // 2, 1)
+            ani.set_option("prune_absent_species", 0)
+            dtd, phd = wl.timed_run(n2, args.warmup)
+            dense_pass = {"ms_per_step": dtd / n2 * 1e3, "value": n2 / dtd * 0.0432,
+                          "phase_ms": {k: phd[k] / max(phd["calls"], 1) for k in ("compact", "aev_fwd", "mlp", "aev_bwd")}}
+            fl = mlp_flops_per_step(model, np.bincount(system.types - 1, minlength=model.num_species))
+            dense_pass["mlp_algorithmic_fp32_tflops"] = fl / (dense_pass["phase_ms"]["mlp"] * 1e-3) / 1e12
+            dense_pass["mlp_frac_of_16bit_mfma_peak"] = 6.0 * dense_pass["mlp_algorithmic_fp32_tflops"] / PEAK_16BIT_MFMA_TFLOPS
+            ani.set_option("prune_absent_species", 1)
+        dt_hot, ph_hot = wl.timed_run(args.steps, args.warmup)
+        energy_local = float(wl.d_ev[0].item())
+        if not np.isfinite(energy_local) and not os.environ.get("ANI_BENCH_ALLOW_NAN"):   # the variable: timing-only ablation builds
+            raise SystemExit("non-finite energy: LDS neighbour capacity exceeded or numerical failure")
+        aev_cols = ani.debug_view().aev_active_length  # columns of the species present (1008 when all 7 occur)
+        mlp_kernel_name = ani.last_mlp_kernel()
+        if args.no_md and args.dump_outputs:
+            # what compute() hands its caller: the forces of the owned atoms (ghost forces folded in) and the energy
+            dumped = gather_outputs(inp.tag[: inp.nlocal], {"forces": wl.d_f.view(-1, 3)[: inp.nlocal].cpu().numpy()},
+                                    {"energy": energy_local})
+    else:
+        system = hx.spatial_sort(hx.water_box(args.atoms, seed=12345))   # the box Workload makes
 
     # ---- the MD loop: the headline -----------------------------------------------------------------------------------
     if args.no_md:
         dt, phases, md_info = dt_hot, ph_hot, None
     else:
-        dt, phases, md_info, aev_cols = md_pass(system, args.steps, args.warmup, with_parity=not args.no_cpu_baseline)
+        dt, phases, md_info, aev_cols, dumped = md_pass(system, args.steps, args.warmup,
+                                                        with_parity=not args.no_cpu_baseline,
+                                                        measure_rebuilds=args.full, headline=True)
         if not md_info["energy_finite"]:
             raise SystemExit("non-finite energy in the MD loop")
     nl, nt, npairs = (md_info["nlocal_rank0"], md_info["nlocal_rank0"] + md_info["nghost_rank0"], md_info["npairs_rank0"]) \
@@ -530,100 +614,101 @@ def main():
                 ns_day = 0.0432 / (ms_per_step * 1e-3)
                 value_basis = ("the K timed steps contained no re-neighbouring and would overstate the loop: value is the rate of the longer "
                                "window that follows them in the same run, re-neighbourings included (md_loop.long_window)")
-        if phases["calls"] == 0:   # the cut step of the overlapped exchange records no phase events: the hot-path pass has them
-            phases = ph_hot
+        if phases["calls"] == 0 and wl is not None:   # the cut step of the overlapped exchange records no phase events: the
+            phases = ph_hot                            # hot-path pass has them
         calls = max(phases["calls"], 1)
         t_cmp, t_fwd, t_mlp, t_bwd, t_other = (phases[k] / calls for k in ("compact", "aev_fwd", "mlp", "aev_bwd", "other"))
-        counts = np.bincount(system.types - 1, minlength=model.num_species) * (nl / system.natoms)
-        flops = mlp_flops_per_step(model, counts, aev_cols)
-        flops_dense = mlp_flops_per_step(model, counts)
-        bf, bb = aev_bytes_per_step(aev_cols, nl, nt, npairs)
+        if args.full:   # roofline of the three kernels of the step
+            counts = np.bincount(system.types - 1, minlength=model.num_species) * (nl / system.natoms)
+            flops = mlp_flops_per_step(model, counts, aev_cols)
+            flops_dense = mlp_flops_per_step(model, counts)
+            bf, bb = aev_bytes_per_step(aev_cols, nl, nt, npairs)
 
-        # counters of a committed rocprofv3 --pmc run count only if they were taken on exactly these kernel sources
-        pmc, pmc_note = None, f"no PMC summary for these kernel sources (profiles/{PMC_SUMMARY} is absent or was measured on other code)"
-        pmc_file = os.path.join(ROOT, "profiles", PMC_SUMMARY)
-        if world == 1 and (args.atoms, args.models) == (100002, 1) and not args.dense_aev and os.path.exists(pmc_file):
-            cand = json.load(open(pmc_file))
-            if cand.get("source_digest") == source_digest():
-                pmc, pmc_note = cand["kernels"], f"profiles/{PMC_SUMMARY} (same kernel sources: digest " + cand["source_digest"] + ")"
+            # counters of a committed rocprofv3 --pmc run count only if they were taken on exactly these kernel sources
+            pmc, pmc_note = None, f"no PMC summary for these kernel sources (profiles/{PMC_SUMMARY} is absent or was measured on other code)"
+            pmc_file = os.path.join(ROOT, "profiles", PMC_SUMMARY)
+            if world == 1 and (args.atoms, args.models) == (100002, 1) and not args.dense_aev and os.path.exists(pmc_file):
+                cand = json.load(open(pmc_file))
+                if cand.get("source_digest") == source_digest():
+                    pmc, pmc_note = cand["kernels"], f"profiles/{PMC_SUMMARY} (same kernel sources: digest " + cand["source_digest"] + ")"
 
-        def counter(prefix, name):
-            if not pmc:
-                return None
-            vals = [c[name]["mean_per_launch"] * c[name].get("launches_per_step", 1) for k, c in pmc.items() if k.startswith(prefix) and name in c]
-            return sum(vals) if vals else None
+            def counter(prefix, name):
+                if not pmc:
+                    return None
+                vals = [c[name]["mean_per_launch"] * c[name].get("launches_per_step", 1) for k, c in pmc.items() if k.startswith(prefix) and name in c]
+                return sum(vals) if vals else None
 
-        def hbm_traffic(prefix):
-            f, w = counter(prefix, "FETCH_SIZE"), counter(prefix, "WRITE_SIZE")
-            # KB; FETCH_SIZE doubled: gfx950 counts half of a wide read (MI355X_MICROARCH.md, HBM)
-            return (2.0 * f + w) * 1024.0 if f is not None and w is not None else None
+            def hbm_traffic(prefix):
+                f, w = counter(prefix, "FETCH_SIZE"), counter(prefix, "WRITE_SIZE")
+                # KB; FETCH_SIZE doubled: gfx950 counts half of a wide read
+                return (2.0 * f + w) * 1024.0 if f is not None and w is not None else None
 
-        def valu(prefix, t_ms):
-            n = counter(prefix, "SQ_INSTS_VALU")
-            # share of the chip's plain-FMA issue slots (one wave64 v_fma_f32 per 2.4 cycles and SIMD, tools/pk_probe.hip);
-            # transcendentals, DPP and integer instructions hold a slot longer, so the pipes are busier than this says
-            return n * 2.4 / (1024 * 2.4e9 * t_ms * 1e-3) if n and t_ms > 0 else None
+            def valu(prefix, t_ms):
+                n = counter(prefix, "SQ_INSTS_VALU")
+                # share of the chip's plain-FMA issue slots (one wave64 v_fma_f32 per 2.4 cycles and SIMD, tools/pk_probe.hip);
+                # transcendentals, DPP and integer instructions hold a slot longer, so the pipes are busier than this says
+                return n * 2.4 / (1024 * 2.4e9 * t_ms * 1e-3) if n and t_ms > 0 else None
 
-        def valu4(prefix, t_ms):
-            # the same count at the four cycles a wave64 fp32 instruction is seen to hold a SIMD's vector unit in these
-            # kernels (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 4.2 cycles; phase stamps + ISA counts), at the
-            # nominal 2.4 GHz -- the chip clocks lower under load, so the units are busier still
-            n = counter(prefix, "SQ_INSTS_VALU")
-            return n * 4.0 / (1024 * 2.4e9 * t_ms * 1e-3) if n and t_ms > 0 else None
+            def valu4(prefix, t_ms):
+                # the same count at the four cycles a wave64 fp32 instruction is seen to hold a SIMD's vector unit in these
+                # kernels (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 4.2 cycles; phase stamps + ISA counts), at the
+                # nominal 2.4 GHz -- the chip clocks lower under load, so the units are busier still
+                n = counter(prefix, "SQ_INSTS_VALU")
+                return n * 4.0 / (1024 * 2.4e9 * t_ms * 1e-3) if n and t_ms > 0 else None
 
-        # useful work of the AEV passes (this rank's share), for their compute bound
-        n_rad, n_ang, n_tri = neighbour_statistics(inp, *ani.cutoffs())
-        share = nl / max(inp.nlocal, 1)
-        n_rad, n_tri = n_rad * share, n_tri * share
-        aev_note = ("bound by the CUs' vector issue, not by HBM (DESIGN.md 3.1): `frac` is the HBM fraction SURVEY 8(d) asks for "
-                    "(algorithmic bytes / time / 8 TB/s); compute_bound_ms = the useful lane-operations and transcendentals of "
-                    "the pass (bench.py AEV_OPS: counts per radial entry and per triple x this structure's entries) at the "
-                    "vector unit's measured issue rate (2.6 cycles per wave64 instruction and SIMD, a transcendental 5x, "
-                    "1024 SIMDs, 2.4 GHz); compute_frac = compute_bound_ms / time; valu_frac_4cyc = SQ_INSTS_VALU x 4 cycles / "
-                    "(1024 SIMDs x time x 2.4 GHz): how busy the vector units are with the instructions the kernel executes")
-        cb_b, cb_f = aev_compute_bound_ms("bwd", n_rad, n_tri), aev_compute_bound_ms("fwd", n_rad, n_tri)
-        bwd_roof = dict(bound="hbm", achieved=bb / (t_bwd * 1e-3) / 1e9 if t_bwd > 0 else None, peak=PEAK_HBM_GBS, unit="GB/s",
-                        traffic=hbm_traffic("ani::aev_backward"), kernel="aev_backward_fast", ms_per_launch=t_bwd, bytes_per_launch=bb,
-                        compute_bound_ms=cb_b, compute_frac=cb_b / t_bwd if t_bwd > 0 else None,
-                        valu_frac=valu("ani::aev_backward", t_bwd), valu_frac_4cyc=valu4("ani::aev_backward", t_bwd),
-                        radial_entries=n_rad, triples=n_tri, note=aev_note, counters=pmc_note)
-        bwd_roof["frac"] = bwd_roof["achieved"] / PEAK_HBM_GBS if bwd_roof["achieved"] else None
-        t_f = t_fwd + t_cmp
-        fwd_roof = dict(bound="hbm", achieved=bf / (t_f * 1e-3) / 1e9 if t_f > 0 else None, peak=PEAK_HBM_GBS, unit="GB/s",
-                        traffic=(hbm_traffic("ani::aev_forward") or 0) + (hbm_traffic("ani::nbr_compact") or 0) if pmc else None,
-                        kernel=("aev_forward_fused" if t_cmp < 0.25 * t_fwd and t_cmp < 0.02 else "nbr_compact_kernel + aev_forward_fast"),
-                        kernel_note="neighbour compaction + AEV forward in one launch" if t_cmp < 0.25 * t_fwd and t_cmp < 0.02 else None,
-                        ms_per_launch=t_f, ms_compact=t_cmp, ms_forward=t_fwd, bytes_per_launch=bf,
-                        compute_bound_ms=cb_f, compute_frac=cb_f / t_f if t_f > 0 else None,
-                        valu_frac=valu("ani::aev_forward", t_fwd), valu_frac_4cyc=valu4("ani::aev_forward", t_fwd),
-                        radial_entries=n_rad, triples=n_tri, note=aev_note, counters=pmc_note)
-        fwd_roof["frac"] = fwd_roof["achieved"] / PEAK_HBM_GBS if fwd_roof["achieved"] else None
-        # The MLP against its bound: the matrix pipe.  The library default evaluates an fp32 product EXACTLY as six bf16 MFMA
-        # products (mlp_arith 1), so the pipe it runs on is the 16-bit one and executes 6x the algorithmic flops:
-        # frac = products x algorithmic flops / time / 2.5 PFLOP/s.
-        nprod = {0: 1, 1: 6, 2: 3}[md_info["mlp_arith"] if md_info else 1]
-        mlp_tr = (hbm_traffic("ani::mlp_fused") or hbm_traffic("ani::mlp_pipeline") or hbm_traffic("ani::gemm_grouped") or
-                  hbm_traffic("ani::mlp_chain"))
-        mlp_peak = PEAK_16BIT_MFMA_TFLOPS if nprod > 1 else PEAK_F32_MFMA_TFLOPS
-        mlp_exec_tf = flops * nprod / (t_mlp * 1e-3) / 1e12 if t_mlp > 0 else None
-        mlp_roof = dict(bound="mfma", achieved=mlp_exec_tf, peak=mlp_peak, unit="TFLOP/s", traffic=mlp_tr,
-                        kernel=mlp_kernel_name, ms_per_launch=t_mlp, flops_per_launch=flops * nprod,
-                        algorithmic_fp32_flops=flops, algorithmic_fp32_flops_full_width_aev=flops_dense, aev_columns=aev_cols,
-                        mfma_products_per_fp32_product=nprod,
-                        algorithmic_fp32_tflops=flops / (t_mlp * 1e-3) / 1e12 if t_mlp > 0 else None,
-                        hbm_frac=(mlp_tr / (t_mlp * 1e-3) / 1e9 / PEAK_HBM_GBS) if (mlp_tr and t_mlp > 0) else None,
-                        note="MLP forward + backward of every species bucket and member in one launch; achieved = the MFMA flops "
-                             "executed (algorithmic fp32 flops 4 M sum_s n_s P_s over the AEV columns in use x MFMA products per fp32 "
-                             "product) / the launch's average duration; peak = the dense peak of the pipe they run on "
-                             "(/opt/skills/guides/MI355X_MICROARCH.md); hbm_frac = counter traffic / time / 8 TB/s",
-                        counters=pmc_note)
-        mlp_roof["frac"] = mlp_exec_tf / mlp_peak if mlp_exec_tf else None
-        # counter view of the same thing: cycles the matrix pipes were busy / (4 SIMDs x cycles a CU was busy), while the launch ran
-        mb, cb = counter("ani::mlp_fused", "SQ_VALU_MFMA_BUSY_CYCLES"), counter("ani::mlp_fused", "SQ_BUSY_CU_CYCLES")
-        mlp_roof["mfma_busy_share"] = mb / (4.0 * cb) if mb and cb else None
-        # `roofline` is the kernel with the largest share of the step (row 1 of the rocprofv3 --stats summary of this command)
-        roofs = sorted([(t_mlp, mlp_roof), (t_bwd, bwd_roof), (t_f, fwd_roof)], key=lambda r: -r[0])
-        main_roof, other_roofs = roofs[0][1], [r[1] for r in roofs[1:]]
+            # useful work of the AEV passes (this rank's share), for their compute bound
+            n_rad, n_ang, n_tri = neighbour_statistics(inp, *ani.cutoffs())
+            share = nl / max(inp.nlocal, 1)
+            n_rad, n_tri = n_rad * share, n_tri * share
+            aev_note = ("bound by the CUs' vector issue, not by HBM (DESIGN.md 3.1): `frac` is the HBM fraction SURVEY 8(d) asks for "
+                        "(algorithmic bytes / time / 8 TB/s); compute_bound_ms = the useful lane-operations and transcendentals of "
+                        "the pass (bench.py AEV_OPS: counts per radial entry and per triple x this structure's entries) at the "
+                        "vector unit's measured issue rate (2.6 cycles per wave64 instruction and SIMD, a transcendental 5x, "
+                        "1024 SIMDs, 2.4 GHz); compute_frac = compute_bound_ms / time; valu_frac_4cyc = SQ_INSTS_VALU x 4 cycles / "
+                        "(1024 SIMDs x time x 2.4 GHz): how busy the vector units are with the instructions the kernel executes")
+            cb_b, cb_f = aev_compute_bound_ms("bwd", n_rad, n_tri), aev_compute_bound_ms("fwd", n_rad, n_tri)
+            bwd_roof = dict(bound="hbm", achieved=bb / (t_bwd * 1e-3) / 1e9 if t_bwd > 0 else None, peak=PEAK_HBM_GBS, unit="GB/s",
+                            traffic=hbm_traffic("ani::aev_backward"), kernel="aev_backward_fast", ms_per_launch=t_bwd, bytes_per_launch=bb,
+                            compute_bound_ms=cb_b, compute_frac=cb_b / t_bwd if t_bwd > 0 else None,
+                            valu_frac=valu("ani::aev_backward", t_bwd), valu_frac_4cyc=valu4("ani::aev_backward", t_bwd),
+                            radial_entries=n_rad, triples=n_tri, note=aev_note, counters=pmc_note)
+            bwd_roof["frac"] = bwd_roof["achieved"] / PEAK_HBM_GBS if bwd_roof["achieved"] else None
+            t_f = t_fwd + t_cmp
+            fwd_roof = dict(bound="hbm", achieved=bf / (t_f * 1e-3) / 1e9 if t_f > 0 else None, peak=PEAK_HBM_GBS, unit="GB/s",
+                            traffic=(hbm_traffic("ani::aev_forward") or 0) + (hbm_traffic("ani::nbr_compact") or 0) if pmc else None,
+                            kernel=("aev_forward_fused" if t_cmp < 0.25 * t_fwd and t_cmp < 0.02 else "nbr_compact_kernel + aev_forward_fast"),
+                            kernel_note="neighbour compaction + AEV forward in one launch" if t_cmp < 0.25 * t_fwd and t_cmp < 0.02 else None,
+                            ms_per_launch=t_f, ms_compact=t_cmp, ms_forward=t_fwd, bytes_per_launch=bf,
+                            compute_bound_ms=cb_f, compute_frac=cb_f / t_f if t_f > 0 else None,
+                            valu_frac=valu("ani::aev_forward", t_fwd), valu_frac_4cyc=valu4("ani::aev_forward", t_fwd),
+                            radial_entries=n_rad, triples=n_tri, note=aev_note, counters=pmc_note)
+            fwd_roof["frac"] = fwd_roof["achieved"] / PEAK_HBM_GBS if fwd_roof["achieved"] else None
+            # The MLP against its bound: the matrix pipe.  The library default evaluates an fp32 product EXACTLY as six bf16 MFMA
+            # products (mlp_arith 1), so the pipe it runs on is the 16-bit one and executes 6x the algorithmic flops:
+            # frac = products x algorithmic flops / time / 2.5 PFLOP/s.
+            nprod = {0: 1, 1: 6, 2: 3}[md_info["mlp_arith"] if md_info else 1]
+            mlp_tr = (hbm_traffic("ani::mlp_fused") or hbm_traffic("ani::mlp_pipeline") or hbm_traffic("ani::gemm_grouped") or
+                      hbm_traffic("ani::mlp_chain"))
+            mlp_peak = PEAK_16BIT_MFMA_TFLOPS if nprod > 1 else PEAK_F32_MFMA_TFLOPS
+            mlp_exec_tf = flops * nprod / (t_mlp * 1e-3) / 1e12 if t_mlp > 0 else None
+            mlp_roof = dict(bound="mfma", achieved=mlp_exec_tf, peak=mlp_peak, unit="TFLOP/s", traffic=mlp_tr,
+                            kernel=mlp_kernel_name, ms_per_launch=t_mlp, flops_per_launch=flops * nprod,
+                            algorithmic_fp32_flops=flops, algorithmic_fp32_flops_full_width_aev=flops_dense, aev_columns=aev_cols,
+                            mfma_products_per_fp32_product=nprod,
+                            algorithmic_fp32_tflops=flops / (t_mlp * 1e-3) / 1e12 if t_mlp > 0 else None,
+                            hbm_frac=(mlp_tr / (t_mlp * 1e-3) / 1e9 / PEAK_HBM_GBS) if (mlp_tr and t_mlp > 0) else None,
+                            note="MLP forward + backward of every species bucket and member in one launch; achieved = the MFMA flops "
+                                 "executed (algorithmic fp32 flops 4 M sum_s n_s P_s over the AEV columns in use x MFMA products per fp32 "
+                                 "product) / the launch's average duration; peak = the dense peak of the pipe they run on "
+                                 "(the MI355X datasheet figure); hbm_frac = counter traffic / time / 8 TB/s",
+                            counters=pmc_note)
+            mlp_roof["frac"] = mlp_exec_tf / mlp_peak if mlp_exec_tf else None
+            # counter view of the same thing: cycles the matrix pipes were busy / (4 SIMDs x cycles a CU was busy), while the launch ran
+            mb, cb = counter("ani::mlp_fused", "SQ_VALU_MFMA_BUSY_CYCLES"), counter("ani::mlp_fused", "SQ_BUSY_CU_CYCLES")
+            mlp_roof["mfma_busy_share"] = mb / (4.0 * cb) if mb and cb else None
+            # `roofline` is the kernel with the largest share of the step (row 1 of the rocprofv3 --stats summary of this command)
+            roofs = sorted([(t_mlp, mlp_roof), (t_bwd, bwd_roof), (t_f, fwd_roof)], key=lambda r: -r[0])
+            main_roof, other_roofs = roofs[0][1], [r[1] for r in roofs[1:]]
 
         what = "static positions, list reused (hot path only)" if args.no_md else \
             ("velocity Verlet + Langevin 300 K, dt 0.5 fs, skin 2.0, rebuild check every 10 steps, all on the device: the "
@@ -640,7 +725,7 @@ def main():
             "dtype_note": "fp32 in/out and accumulation everywhere; the MLP's fp32 products are EXACT: both operands split into three bf16 "
                           "terms (8+8+8 mantissa bits), six bf16 MFMA products accumulated in fp32, the three dropped terms below "
                           "2^-23 of the product (library default mlp_arith = 1; the reference runs fp32 with TF32 off, "
-                          "src/ani_csrc/ani.cpp:41-43).  `value_f16x2_split` is the same loop with the reduced-precision opt-in "
+                          "src/ani_csrc/ani.cpp:41-43).  `value_f16x2_split` (--full) is the same loop with the reduced-precision opt-in "
                           "(mlp_arith = 2, the counterpart of LAMMPS_ANI_ALLOW_TF32).  fp64 positions, velocities, energy sums",
             "config": {"workload": f"water-{args.atoms} (rho=0.98 g/cm3), ANI-2x shaped seeded weights, {args.models} model(s), "
                                    f"pair_style ani 5.1 <model> hip {args.models} {args.aev} full single; {what}",
@@ -649,14 +734,18 @@ def main():
                        "prune_absent_species": not args.dense_aev, "aev_columns": aev_cols, "backend": backend if world > 1 else None,
                        "matom_steps_per_s": args.atoms * steps / dt / 1e6,
                        "vs_baseline_note": "published numbers are LAMMPS Performance lines on A100s (examples/benchmark/README.md:78-81): other hardware, same metric and workload"},
-            "roofline": main_roof, "roofline_other": other_roofs, "full_width_aev_pass": dense_pass,
-            "phase_ms": {"nbr_compact": t_cmp, "aev_fwd": t_fwd, "mlp": t_mlp, "aev_bwd": t_bwd, "finish": t_other},
+            "phase_ms": {"nbr_compact": t_cmp, "aev_fwd": t_fwd, "mlp": t_mlp, "aev_bwd": t_bwd, "finish": t_other}
+                        if phases["calls"] else None,
             "md_loop": md_info,
-            "hot_path": {"what": "pair_style compute() alone: static positions, list reused (ago > 0), ghost-force exchange included",
-                         "ms_per_step": dt_hot / steps * 1e3, "value": steps / dt_hot * 0.0432, "unit": "ns/day",
-                         "phase_ms": {k: ph_hot[k] / max(ph_hot["calls"], 1) for k in ("compact", "aev_fwd", "mlp", "aev_bwd", "other")}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                "roofline": main_roof, "roofline_other": other_roofs, "full_width_aev_pass": dense_pass,
+                "hot_path": {"what": "pair_style compute() alone: static positions, list reused (ago > 0), ghost-force exchange included",
+                             "ms_per_step": dt_hot / steps * 1e3, "value": steps / dt_hot * 0.0432, "unit": "ns/day",
+                             "phase_ms": {k: ph_hot[k] / max(ph_hot["calls"], 1) for k in ("compact", "aev_fwd", "mlp", "aev_bwd", "other")}},
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import Oracle
             o = Oracle(wl.mpath)  # fp64 restatement, OpenMP over all host cores
             ref = o.compute(inp, radial_compat=(args.aev == "pyaev"))   # warm-up (page faults, thread pool), kept for the parity check
@@ -695,19 +784,22 @@ def main():
                     "max_abs_force_diff_to_default_path": float(np.abs(f32[: inp.nlocal] - f[: inp.nlocal]).max()),
                     "mlp_ms_per_step": ph32["mlp"] / max(ph32["calls"], 1)}
             ani.set_option("mlp_arith", 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and dumped is not None:
+        write_outputs(args.dump_outputs, *dumped)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["adapter_path"] = adapter_path(inp, wl.mpath)
-    wl.close()
-    if rank == 0 and world == 1 and not args.no_md and not args.no_extra:
+    if wl is not None:
+        wl.close()
+    if args.full and rank == 0 and world == 1 and not args.no_md and not args.no_extra:
         # labelled secondary: the same MD loop with the reduced-precision opt-in (two-term fp16 splits, three MFMA products)
         k2 = min(args.steps, 100)
-        dt2x, _, info2x, _ = md_pass(system, k2, min(args.warmup, 10), arith=2, measure_rebuilds=False)
+        dt2x, _, info2x, _, _ = md_pass(system, k2, min(args.warmup, 10), arith=2, measure_rebuilds=False)
         out["value_f16x2_split"] = {"value": k2 / dt2x * 0.0432, "unit": "ns/day", "ms_per_step": dt2x / k2 * 1e3, "steps": k2,
                                     "list_rebuilds": info2x["list_rebuilds"],
                                     "what": "option mlp_arith = 2 (LAMMPS_ANI_ALLOW_TF32=1): operands to 2^-22 instead of exact; NOT the "
                                             "headline; force error against the oracle in parity.f16x2_split_path"}
 
-    if rank == 0 and world == 1 and not args.no_extra and (args.atoms, args.models) == (100002, 1):
+    if args.full and rank == 0 and world == 1 and not args.no_extra and (args.atoms, args.models) == (100002, 1):
         # BASELINE.json configs[1]: full 8-member ensemble on a ~10k-atom water box (hot path; not the headline value)
         args_models = args.models
         w2 = Workload(10002, 8)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--atoms", "3000", "--steps", "8", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--atoms", "3000", "--steps", "8", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -62,7 +63,7 @@ def test_the_timed_steps_carry_no_first_use_costs():
     it uses, the event pool of the phase timers) must have been paid before — `md.VerletRun.warm_paths`,
     `ani_phase_timing`.  Without that the same command measured 1.7 to 5 times the plain step."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--atoms", "24000", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-dense-pass", "--no-extra"], capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-dense-pass", "--no-extra", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
     md, hot = d["md_loop"]["ms_per_step"], d["hot_path"]["ms_per_step"]
@@ -70,3 +71,63 @@ def test_the_timed_steps_carry_no_first_use_costs():
     allowance = 0.10 * d["md_loop"]["list_rebuilds"]          # ms per step that one re-neighbouring among 20 steps may add
     assert md < 1.25 * hot + 0.03 + allowance, (md, hot, d["md_loop"])
 
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full prints the headline and nothing that takes runs of its own; with
+    --dump-outputs it writes the state the last of the K timed MD steps left, one row per atom in global order."""
+    out = tmp_path / "md"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--atoms", "3000", "--steps", "8", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, f"stdout must carry only the JSON line, got {len(lines)} lines"
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "value_basis", "md_loop"):
+        assert k in d, k
+    assert "MD ns/day" in d["metric"] and d["unit"] == "ns/day" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 8 and d["warmup"] == 2
+    assert abs(d["value"] - 0.0432 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "parity", "roofline", "hot_path", "full_width_aev_pass", "adapter_path", "value_f16x2_split",
+              "extra_config", "mixed_species_config"):
+        assert k not in d, k
+    md = d["md_loop"]
+    assert md["steps"] == 8 and md["energy_finite"]
+    for k in ("parity_md_model", "rebuild_ms", "sustained_window"):
+        assert k not in md, k
+    # the headline keeps its meaning: K steps without a re-neighbouring give way to the longer window that follows them
+    if md["list_rebuilds"] > 0:
+        assert abs(md["ms_per_step"] - d["ms_per_step"]) < 1e-9 and "long_window" not in md
+    else:
+        assert abs(md["amortised_ms_per_step"] - d["ms_per_step"]) < 1e-9 and md["long_window"]["list_rebuilds"] > 0
+    assert sorted(p.name for p in out.iterdir()) == ["forces.npy", "positions.npy", "potential_energy.npy", "velocities.npy"]
+    for name in ("positions", "velocities", "forces"):
+        a = np.load(out / f"{name}.npy")
+        assert a.shape == (3000, 3) and a.dtype == np.float64 and np.isfinite(a).all(), name
+        assert np.abs(a).max() > 0, name
+    e = np.load(out / "potential_energy.npy")
+    assert e.shape == (1,) and e.dtype == np.float64 and np.isfinite(e).all()
+
+
+def test_hot_path_dump_matches_the_oracle(tmp_path):
+    """--no-md --dump-outputs: the forces and energy of the last timed hot-path step, rows in global atom order, are those
+    of the CPU oracle on the same seeded box and model."""
+    from lammps_ani_amd import harness as hx, model_file as mf   # loaded by conftest
+    from oracle import Oracle
+    out = tmp_path / "hot"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--atoms", "3000", "--steps", "4", "--warmup", "1", "--no-md",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(p.name for p in out.iterdir()) == ["energy.npy", "forces.npy"]
+    f, e = np.load(out / "forces.npy"), np.load(out / "energy.npy")
+    # the workload bench.py's hot path runs: seeded box, spatially sorted, one rank, the seeded ANI-2x shaped model
+    inp = hx.decompose(hx.spatial_sort(hx.water_box(3000, seed=12345)), (1, 1, 1), 0, cutoff=5.1, skin=2.0)
+    path = str(tmp_path / "m.anim")
+    mf.write_model(path, mf.synthetic_model("ani2x", 1, seed=2024))
+    ref = Oracle(path).compute(inp)
+    fr = ref["force"][: inp.nlocal].copy()
+    np.add.at(fr, inp.owner_lidx, ref["force"][inp.nlocal:])
+    fr = fr[np.argsort(inp.tag[: inp.nlocal], kind="stable")]
+    assert f.shape == fr.shape and f.dtype == np.float64
+    assert np.abs(f - fr).max() < 2.3e-3, np.abs(f - fr).max()
+    assert abs(float(e[0]) - ref["energy"]) < 1.2e-4 * 3000 ** 0.5 + 3e-4, (float(e[0]), ref["energy"])

@@ -64,7 +64,7 @@ def test_two_rank_bench_on_one_card_takes_the_fallback_transport():
     touches the GPU), they meet over gloo (RCCL refuses two ranks on one device), try the native communicator, find RCCL
     disabled, agree on that, and fall back to torch.distributed for the ghost exchange -- the sequence a node with a broken
     librccl would take.  The JSON line must keep the driver's contract for N ranks."""
-    r = _run(["--gpus", "2", "--atoms", "6000", "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--no-dense-pass", "--no-extra"],
+    r = _run(["--gpus", "2", "--atoms", "6000", "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--no-dense-pass", "--no-extra", "--full"],
              {"ANI_BENCH_BACKEND": "gloo", "ANI_BENCH_NATIVE_COMM": "try", "ANI_COMM_DISABLE_RCCL": "1",
               "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert r.returncode == 0, r.stderr[-3000:]
