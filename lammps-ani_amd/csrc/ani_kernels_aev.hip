@@ -172,7 +172,7 @@ void launch_sort_jlist(const int* d_species, const int* d_nbr_off, const int* d_
 // The backward kernel's per-neighbour gradient accumulators in LDS take several adds per pair.  On gfx950 an LDS fp32 add
 // (ds_add_f32, also ds_pk_add_f16) is executed ONE LANE AT A TIME, ~3 cycles per active lane -- 192 cycles for a full wave,
 // the CU's LDS blocked meanwhile -- whereas ds_add_f64 takes 8 cycles per wave-instruction, like the integer adds
-// (tools/lds_atomic_probe.hip, profiles/r03_lds_atomic_probe.log).  So the accumulators are doubles: one v_cvt_f64_f32 per
+// (tools/lds_rmw_probe.hip, profiles/r03_lds_rmw_probe.log).  So the accumulators are doubles: one v_cvt_f64_f32 per
 // value added, 6 instead of 3 words per neighbour, and sums that are more accurate on top.
 #ifdef ANI_GD_F32
 typedef float gd_t;

@@ -222,21 +222,28 @@ static void aev_forward(const oracle_model* m, int n, const nbr_t* nb, const cha
   }
 }
 
-/* given g = dE/dAEV of this centre, accumulate gd[p][3] = dE/d(d_p) for every neighbour p */
-static void aev_backward(const oracle_model* m, int n, const nbr_t* nb, const char* rad, const char* ang, const REAL* g, REAL (*gd)[3]) {
+/* given g = dE/dAEV of this centre, accumulate gd[p][3] = dE/d(d_p) for every neighbour p.  gda (may be NULL): the same
+ * sums taken over the absolute values of their terms (every product of the chain rule by its magnitude) */
+static void aev_backward(const oracle_model* m, int n, const nbr_t* nb, const char* rad, const char* ang, const REAL* g, REAL (*gd)[3],
+                         REAL (*gda)[3]) {
   const int nR = m->nR, nA = m->nA, nZ = m->nZ;
   for (int p = 0; p < n; p++) gd[p][0] = gd[p][1] = gd[p][2] = 0;
+  if (gda)
+    for (int p = 0; p < n; p++) gda[p][0] = gda[p][1] = gda[p][2] = 0;
   for (int p = 0; p < n; p++) {
     if (!rad[p]) continue;
     REAL r = nb[p].r, fc = fcut(r, (REAL)m->Rcr), dfc = dfcut(r, (REAL)m->Rcr);
     const REAL* gg = g + nb[p].sp * nR;
-    REAL dEdr = 0;
+    REAL dEdr = 0, dEdr_abs = 0;
     for (int k = 0; k < nR; k++) {
       REAL dr = r - (REAL)m->ShfR[k];
       REAL e = (REAL)0.25 * (REAL)exp((double)(-(REAL)m->EtaR * dr * dr));
       dEdr += gg[k] * (e * dfc - (REAL)2 * (REAL)m->EtaR * dr * e * fc);
+      if (gda) dEdr_abs += (REAL)fabs((double)gg[k]) * (e * (REAL)fabs((double)dfc) + (REAL)2 * (REAL)m->EtaR * (REAL)fabs((double)dr) * e * fc);
     }
     for (int c = 0; c < 3; c++) gd[p][c] += dEdr * nb[p].d[c] / r;
+    if (gda)
+      for (int c = 0; c < 3; c++) gda[p][c] += dEdr_abs * (REAL)fabs((double)nb[p].d[c]) / r;
   }
   for (int p = 0; p < n; p++) {
     if (!ang[p]) continue;
@@ -254,7 +261,7 @@ static void aev_backward(const oracle_model* m, int n, const nbr_t* nb, const ch
       REAL P = fca * fcb, rho = (a->r + b->r) * (REAL)0.5;
       const REAL* gg = g + m->radial_len + m->triu[a->sp][b->sp] * nA * nZ;
       /* A: dE/dcos(theta) ; Bq: dE/drho ; C: sum g*2*f1*f2 (multiplies d(fca fcb)) */
-      REAL A = 0, Bq = 0, C = 0;
+      REAL A = 0, Bq = 0, C = 0, Aa = 0, Ba = 0, Ca = 0;
       for (int ia = 0; ia < nA; ia++) {
         REAL dr = rho - (REAL)m->ShfA[ia];
         REAL f2 = (REAL)exp((double)(-(REAL)m->EtaA * dr * dr));
@@ -269,12 +276,25 @@ static void aev_backward(const oracle_model* m, int n, const nbr_t* nb, const ch
           A += gv * (REAL)2 * P * f2 * df1 * (REAL)0.95;
           Bq += gv * (REAL)2 * P * f1 * df2;
           C += gv * (REAL)2 * f1 * f2;
+          if (gda) {
+            const REAL av = (REAL)fabs((double)gv);
+            Aa += av * (REAL)2 * P * f2 * (REAL)fabs((double)df1) * (REAL)0.95;
+            Ba += av * (REAL)2 * P * f1 * (REAL)fabs((double)df2);
+            Ca += av * (REAL)2 * f1 * f2;
+          }
         }
       }
       for (int c = 0; c < 3; c++) {
         REAL ua = a->d[c] / a->r, ub = b->d[c] / b->r;
         gd[p][c] += A * (b->d[c] / rr - cosv * a->d[c] / (a->r * a->r)) + (Bq * (REAL)0.5 + C * dfa * fcb) * ua;
         gd[q][c] += A * (a->d[c] / rr - cosv * b->d[c] / (b->r * b->r)) + (Bq * (REAL)0.5 + C * fca * dfb) * ub;
+        if (gda) {
+          const REAL fa = (REAL)fabs((double)ua), fb = (REAL)fabs((double)ub), ca = (REAL)fabs((double)cosv);
+          gda[p][c] += Aa * ((REAL)fabs((double)b->d[c]) / rr + ca * (REAL)fabs((double)a->d[c]) / (a->r * a->r)) +
+                       (Ba * (REAL)0.5 + Ca * (REAL)fabs((double)(dfa * fcb))) * fa;
+          gda[q][c] += Aa * ((REAL)fabs((double)a->d[c]) / rr + ca * (REAL)fabs((double)b->d[c]) / (b->r * b->r)) +
+                       (Ba * (REAL)0.5 + Ca * (REAL)fabs((double)(fca * dfb))) * fb;
+        }
       }
     }
   }
@@ -439,7 +459,7 @@ static int compute_core(const oracle_model* m, int ntotal, int ncentre, const in
     for (int c = 0; c < ncentre; c++) {
       int i = centre[c];
       int n = gather(m, i, species, x, off + c, nj, compat, nb, rad, ang);
-      aev_backward(m, n, nb, rad, ang, gaev + (size_t)c * A, gd);
+      aev_backward(m, n, nb, rad, ang, gaev + (size_t)c * A, gd, NULL);
       if (m->has_rep) {
         double er = 0;
         for (int p = 0; p < n; p++) {
@@ -528,6 +548,82 @@ int ani_oracle_compute_half(const oracle_model* m, int ntotal, int nlocal, const
   int rc = compute_core(m, ntotal, nlocal, centre, off, nj, species, x, radial_compat, energy, force, eatom, virial, aev_out, gaev_out);
   free(off); free(nj); free(fill); free(centre);
   return rc;
+}
+
+/*
+ * Pass C of compute_core alone (no repulsion): forces and virial of a CALLER-SUPPLIED dE/dAEV (gaev_in [nlocal][aev_len],
+ * Hartree, centre order of a full list as ani_oracle_compute_full takes it).  force [ntotal*3] (overwritten) and
+ * virial [9] as compute_core returns them.  force_abs / virial_abs (may be NULL): the same sums over the absolute values of
+ * every term that goes into them (the magnitudes of error bars).  A model with repulsion is refused (-3): its pair forces
+ * do not go through dE/dAEV.
+ */
+int ani_oracle_aev_vjp(const oracle_model* m, int ntotal, int nlocal, const int64_t* species, const double* x, const int* ilist,
+                       const int* numneigh, const int* jlist, int radial_compat, const REAL* gaev_in, double* force, double* virial,
+                       double* force_abs, double* virial_abs) {
+  if (m->has_rep) return -3;
+  const int A = m->aev_len;
+  int64_t* off = (int64_t*)malloc(sizeof(int64_t) * (nlocal + 1));
+  off[0] = 0;
+  int maxn = 0;
+  for (int c = 0; c < nlocal; c++) {
+    off[c + 1] = off[c] + numneigh[c];
+    if (numneigh[c] > maxn) maxn = numneigh[c];
+  }
+  for (int c = 0; c < nlocal; c++) { int s = (int)species[ilist[c]]; if (s < 0 || s >= m->S) { free(off); return -2; } }
+  memset(force, 0, sizeof(double) * 3 * (size_t)ntotal);
+  if (force_abs) memset(force_abs, 0, sizeof(double) * 3 * (size_t)ntotal);
+  double vir[9] = {0}, vira[9] = {0};
+#pragma omp parallel
+  {
+    nbr_t* nb = (nbr_t*)malloc(sizeof(nbr_t) * (maxn + 1));
+    char* rad = (char*)malloc(maxn + 1);
+    char* ang = (char*)malloc(maxn + 1);
+    REAL(*gd)[3] = (REAL(*)[3])malloc(sizeof(REAL) * 3 * (maxn + 1));
+    REAL(*gda)[3] = (REAL(*)[3])malloc(sizeof(REAL) * 3 * (maxn + 1));
+    double v[9] = {0}, va[9] = {0};
+#pragma omp for schedule(dynamic, 16)
+    for (int c = 0; c < nlocal; c++) {
+      int i = ilist[c];
+      int n = gather(m, i, species, x, off + c, jlist, radial_compat, nb, rad, ang);
+      aev_backward(m, n, nb, rad, ang, gaev_in + (size_t)c * A, gd, gda);
+      double fi[3] = {0, 0, 0}, fia[3] = {0, 0, 0};
+      for (int p = 0; p < n; p++) {
+        for (int k = 0; k < 3; k++) {
+          double gk = (double)gd[p][k] * HARTREE2KCALMOL, ga = (double)gda[p][k] * HARTREE2KCALMOL;
+          fi[k] += gk;
+          fia[k] += ga;
+#pragma omp atomic
+          force[3 * nb[p].j + k] -= gk;
+          if (force_abs) {
+#pragma omp atomic
+            force_abs[3 * nb[p].j + k] += ga;
+          }
+          for (int l = 0; l < 3; l++) {
+            v[3 * k + l] -= gk * (double)nb[p].d[l];
+            va[3 * k + l] += ga * fabs((double)nb[p].d[l]);
+          }
+        }
+      }
+      for (int k = 0; k < 3; k++) {
+#pragma omp atomic
+        force[3 * i + k] += fi[k];
+        if (force_abs) {
+#pragma omp atomic
+          force_abs[3 * i + k] += fia[k];
+        }
+      }
+    }
+#pragma omp critical
+    for (int k = 0; k < 9; k++) { vir[k] += v[k]; vira[k] += va[k]; }
+    free(nb); free(rad); free(ang); free(gd); free(gda);
+  }
+  for (int k = 0; k < 3; k++)
+    for (int l = 0; l < 3; l++) {
+      if (virial) virial[3 * k + l] = 0.5 * (vir[3 * k + l] + vir[3 * l + k]);
+      if (virial_abs) virial_abs[3 * k + l] = 0.5 * (vira[3 * k + l] + vira[3 * l + k]);
+    }
+  free(off);
+  return 0;
 }
 
 int ani_oracle_num_threads(void) {

@@ -38,6 +38,7 @@ class Oracle:
         lib.ani_oracle_compute_full.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 6
         lib.ani_oracle_compute_half.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                                 C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        lib.ani_oracle_aev_vjp.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
         self.h = lib.ani_oracle_load(model_file.encode(), use_num_models)
         if not self.h:
             raise RuntimeError(f"oracle: cannot load model {model_file!r} (use_num_models={use_num_models})")
@@ -78,3 +79,38 @@ class Oracle:
         if rc != 0:
             raise RuntimeError(f"oracle compute failed rc={rc}")
         return dict(energy=float(e[0]), force=f, eatom=ea, virial=vir.reshape(3, 3), aev=aev, gaev=gaev)
+
+    def aev_vjp(self, inp, gaev, radial_compat: bool = False):
+        """Pass C alone: forces and virial of the dE/dAEV ``gaev`` [nlocal, aev_len] (Hartree, centre order) supplied by the
+        caller, with the sums of the absolute values of their terms.  A half list is turned into the per-centre lists
+        ani_oracle_compute_half forms (every pair feeds both of its local ends, in pair order).  Models without repulsion
+        only.  Returns dict(force[ntotal,3], virial[3,3], force_abs[ntotal,3], virial_abs[3,3])."""
+        nt, nl = inp.ntotal, inp.nlocal
+        species = np.ascontiguousarray(inp.species, dtype=np.int64)
+        x = np.ascontiguousarray(inp.x, dtype=np.float64)
+        if inp.half:
+            i = np.repeat(inp.ilist.astype(np.int64), inp.numneigh)
+            j = inp.jlist.astype(np.int64)
+            lists = [[] for _ in range(nl)]
+            for a, b in zip(i.tolist(), j.tolist()):
+                if a < nl:
+                    lists[a].append(b)
+                if b < nl:
+                    lists[b].append(a)
+            il = np.arange(nl, dtype=np.int32)
+            nn = np.array([len(q) for q in lists], dtype=np.int32)
+            jl = np.array([b for q in lists for b in q], dtype=np.int32)
+        else:
+            il = np.ascontiguousarray(inp.ilist, dtype=np.int32)
+            nn = np.ascontiguousarray(inp.numneigh, dtype=np.int32)
+            jl = np.ascontiguousarray(inp.jlist, dtype=np.int32)
+        g = np.ascontiguousarray(gaev, dtype=self.real)
+        assert g.shape == (nl, self.aev_len)
+        f, fa = np.zeros((nt, 3)), np.zeros((nt, 3))
+        vir, vira = np.zeros(9), np.zeros(9)
+        rc = self.lib.ani_oracle_aev_vjp(self.h, nt, nl, species.ctypes.data, x.ctypes.data, il.ctypes.data, nn.ctypes.data,
+                                         jl.ctypes.data, int(radial_compat), g.ctypes.data, f.ctypes.data, vir.ctypes.data,
+                                         fa.ctypes.data, vira.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"oracle aev_vjp failed rc={rc}")
+        return dict(force=f, virial=vir.reshape(3, 3), force_abs=fa, virial_abs=vira.reshape(3, 3))

@@ -1,7 +1,7 @@
-// lds_atomic_probe.hip -- what an LDS read-modify-write costs on gfx950, per wave-instruction, when all waves of a CU issue
+// lds_rmw_probe.hip -- what an LDS read-modify-write costs on gfx950, per wave-instruction, when all waves of a CU issue
 // them back to back (the LDS is one unit per CU): float add against integer add, 64-bit add, plain write and read, with 64 /
 // 32 / 8 active lanes and with lanes sharing addresses.  The AEV backward kernel's pair loop issues six ds_add_f32 per step.
-// Build: hipcc --offload-arch=gfx950 -O3 -o lds_atomic_probe lds_atomic_probe.hip
+// Build: hipcc --offload-arch=gfx950 -O3 -o lds_rmw_probe lds_rmw_probe.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #define REP 256
