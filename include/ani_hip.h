@@ -115,6 +115,36 @@ int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_
                             int eflag_atom, int vflag, double* d_f, double* d_ev, double* d_eatom, void* stream);
 
 /*
+ * Per-atom virial, for `compute stress/atom`, `compute centroid/stress/atom` and `compute heat/flux`.  Arms the NEXT step only
+ * (one call of ani_compute_full / ani_compute_half, of ani_compute_full_device, or one ani_step_begin ... ani_step_finish
+ * sequence), the way LAMMPS sets vflag_atom only on the steps a compute reads it; an entry point that fails still takes the arming.
+ *   out     [ntotal][ncomp] doubles, indexed by atom (not in ilist order); host memory for the host entry points, device memory
+ *           (the handle's device) for the device ones.  NULL disarms.
+ *   ncomp   9: LAMMPS cvatom order  xx yy zz xy xz yz yx zx zy;  6: vatom  xx yy zz xy xz yz of the symmetric part.
+ *           Anything else returns ANI_ERR_ARG (and leaves the handle unarmed).
+ * Definition (site-energy form).  E = sum_i E_i with E_i the per-centre energy (out_atomic_energies), and
+ *     W_j = sum over the centres i that have j in their list of  (x_j - x_i) (outer) F_j^(i),   F_j^(i) = -dE_i/dx_j,
+ * "xy" = sum (x_j - x_i)_x F_y, in kcal/mol like out_virial.  This is the per-atom virial that makes
+ * J = sum_j (e_j v_j - W_j . v_j) an exact heat current for that energy split (Fan et al., PRB 92, 094301, 2015): each term goes to
+ * the atom that RECEIVES the force, the term j == i has weight 0.  Consequences: the sum of W_j over all ntotal rows is the
+ * unsymmetrised global virial, its symmetric part the out_virial of the same call; ghost atoms receive terms (their rows belong to
+ * their owners, like ghost force rows); the pairwise repulsion of REPULXTB models, half of the pair term per list entry, splits
+ * half / half between the two atoms of a pair of centres.
+ * Where the rows go follows the force array of the entry point:
+ *   ani_compute_full / _half   every ntotal row is overwritten; the ghost rows hold what belongs to the ghosts and the caller
+ *                              folds them into their owners (LAMMPS: reverse_comm with 9 values per atom when newton is off).
+ *                              Armed with a communicator attached (ani_attach_comm): ANI_ERR_ARG -- no 9-wide reverse exchange.
+ *   ani_compute_full_device    added into out like d_f (overwritten under option device_overwrite_forces), every ntotal row;
+ *                              with a ghost fold installed (ani_set_ghost_fold) the ghost rows are folded into their owners'
+ *                              rows and are NOT written.
+ *   ani_step_begin ... finish  added / overwritten like d_f, every ntotal row (a split step applies no fold): both backward
+ *                              halves add into one accumulator, ani_step_finish writes out.
+ * Both precisions (per-atom accumulators in the handle's precision).  An armed step runs separate instantiations of the backward
+ * kernels, with nine float atomics per scattered term; unarmed steps run exactly the kernels they ran before.
+ */
+int ani_request_atom_virial(ani_handle* h, double* out, int ncomp);
+
+/*
  * Ghosts that are images of the rank's OWN atoms (one rank with periodic boundaries; the self-images of a rank whose brick spans
  * the box in some direction): their two exchanges of a step folded into the step's own first and last kernel.  With a fold
  * installed, ani_compute_full_device

@@ -22,7 +22,8 @@ EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani
            "ani_aev_length", "ani_cutoff_radial", "ani_cutoff_angular", "ani_compute_full", "ani_compute_half",
            "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_set_option", "ani_phase_timing", "ani_phase_times",
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
-           "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold"]
+           "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
+           "ani_request_atom_virial"]
 # include/ani_comm.h: the device-side ghost exchange over RCCL
 COMM_EXPORTS = ["ani_comm_get_unique_id", "ani_comm_create", "ani_comm_create_local", "ani_comm_destroy", "ani_comm_last_error", "ani_comm_rank",
                 "ani_comm_size", "ani_comm_plan", "ani_comm_exchange_counts", "ani_comm_alltoallv", "ani_comm_set_epoch",
@@ -97,6 +98,7 @@ def lib():
         L.ani_last_mlp_kernel.argtypes = [C.c_void_p]
         L.ani_set_ghost_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ani_stage_ghost_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ani_request_atom_virial.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ani_host_register.argtypes = [C.c_void_p, C.c_size_t]
         L.ani_host_unregister.argtypes = [C.c_void_p]
         L.ani_last_mlp_kernel.restype = C.c_char_p
@@ -182,10 +184,23 @@ class ANI:
         if rc != 0:
             raise AniError(f"libani_hip error {rc}: {self._lib.ani_last_error(self._h).decode()}")
 
-    def compute(self, inp, ago: int = 0, eflag_atom: bool = True, vflag: bool = True, force_into=None):
+    def request_atom_virial(self, out, ncomp: int):
+        """ani_request_atom_virial: arm the NEXT step's per-atom virial into ``out`` (host array or device address, [ntotal, ncomp]
+        float64; ncomp 9 = cvatom order, 6 = vatom); None disarms."""
+        if isinstance(out, np.ndarray):
+            assert out.dtype == np.float64 and out.flags.c_contiguous and out.size == out.shape[0] * ncomp
+            out = out.ctypes.data
+        self._check(self._lib.ani_request_atom_virial(self._h, out, int(ncomp)))
+
+    def compute(self, inp, ago: int = 0, eflag_atom: bool = True, vflag: bool = True, force_into=None, atom_virial: int = 0):
         """Host-pointer entry points with a harness.RankInput (full or half list).  Returns a dict like the oracle's.
-        force_into: a C-contiguous float64 [ntotal, 3] array handed over as out_force (option out_force_accumulate adds into it)."""
+        force_into: a C-contiguous float64 [ntotal, 3] array handed over as out_force (option out_force_accumulate adds into it).
+        atom_virial: 6 or 9 adds "atom_virial" [ntotal, atom_virial] (kcal/mol, include/ani_hip.h), 0 = not asked for."""
         nt, nl = inp.ntotal, inp.nlocal
+        av = None
+        if atom_virial:
+            av = np.full((nt, int(atom_virial)), np.nan)
+            self.request_atom_virial(av, int(atom_virial))
         species = np.ascontiguousarray(inp.species, dtype=np.int64)
         x = np.ascontiguousarray(inp.x, dtype=np.float64)
         e = np.zeros(1)
@@ -206,17 +221,27 @@ class ANI:
                                             il.ctypes.data, jl.ctypes.data, nn.ctypes.data, ago, int(eflag_atom),
                                             int(vflag), e.ctypes.data, f.ctypes.data, ea.ctypes.data, vir.ctypes.data)
         self._check(rc)
-        return dict(energy=float(e[0]), force=f, eatom=ea, virial=vir.reshape(3, 3))
+        out = dict(energy=float(e[0]), force=f, eatom=ea, virial=vir.reshape(3, 3))
+        if av is not None:
+            out["atom_virial"] = av
+        return out
 
     def compute_device(self, ntotal, nlocal, d_species, d_x, npairs, d_ilist, d_jlist, d_numneigh, ago, d_f, d_ev,
-                       d_eatom=None, eflag_atom=False, vflag=False, stream=None):
-        """Device-resident step; arguments are raw device addresses (e.g. torch tensor .data_ptr())."""
+                       d_eatom=None, eflag_atom=False, vflag=False, stream=None, d_atom_virial=None, ncomp=9):
+        """Device-resident step; arguments are raw device addresses (e.g. torch tensor .data_ptr()).  d_atom_virial: device
+        [ntotal, ncomp] float64 the per-atom virial is ADDED to (include/ani_hip.h), None = not asked for."""
+        if d_atom_virial is not None:
+            self.request_atom_virial(d_atom_virial, ncomp)
         rc = self._lib.ani_compute_full_device(self._h, ntotal, nlocal, d_species, d_x, npairs, d_ilist, d_jlist,
                                                d_numneigh, ago, int(eflag_atom), int(vflag), d_f, d_ev, d_eatom, stream)
         self._check(rc)
 
-    def step_begin(self, ntotal, nlocal, d_x, d_f, d_ev, d_eatom=None, eflag_atom=False, vflag=False, stream=None):
-        """Split device-resident step, part 1 of 3 (include/ani_hip.h): needs the owned atoms' positions only."""
+    def step_begin(self, ntotal, nlocal, d_x, d_f, d_ev, d_eatom=None, eflag_atom=False, vflag=False, stream=None,
+                   d_atom_virial=None, ncomp=9):
+        """Split device-resident step, part 1 of 3 (include/ani_hip.h): needs the owned atoms' positions only.
+        d_atom_virial: as for compute_device; step_finish writes it."""
+        if d_atom_virial is not None:
+            self.request_atom_virial(d_atom_virial, ncomp)
         self._check(self._lib.ani_step_begin(self._h, ntotal, nlocal, d_x, int(eflag_atom), int(vflag), d_f, d_ev, d_eatom, stream))
 
     def step_ghosts_ready(self, stream=None):

@@ -170,6 +170,16 @@ struct ani_handle {
   hipStream_t side = nullptr;
   hipEvent_t ev_mlp = nullptr, ev_side = nullptr;
   struct { const double* d_x; int eflag_atom, vflag; double *d_f, *d_ev, *d_eatom; } split{};
+  // per-atom virial (ani_request_atom_virial): armed for the next step only; av_acc is the accumulator of the step being run
+  // (cleared by run_step / ani_step_begin, NULL on an unarmed step), split_av the output of an armed split step
+  double* av_out = nullptr;
+  int av_ncomp = 0;
+  void* av_acc = nullptr;
+  double* split_av = nullptr;
+  int split_av_ncomp = 0;
+  DevBuf<float> avir;      // [ntotal][9] accumulator (Hartree) of an armed fp32 step
+  DevBuf<double> avir64;   // ... of an fp64 step
+  DevBuf<double> avout;    // [ntotal][ncomp] the host entry points' result on the device
   int nlocal = 0, ntotal = 0, nrows = 0;
   long long npairs = 0;
   int count[kMaxSpecies] = {0}, row_start[kMaxSpecies] = {0};
@@ -1049,6 +1059,7 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
   HIP_TRY(h, hipMemsetAsync(h->fbuf64.p, 0, sizeof(double) * 3 * (size_t)h->ntotal, st));
   HIP_TRY(h, hipMemsetAsync(h->virial_acc.p, 0, sizeof(double) * 9, st));
   HIP_TRY(h, hipMemsetAsync(h->e_rows64.p, 0, sizeof(double) * (size_t)M * std::max(h->nrows, 1), st));
+  if (h->av_acc) HIP_TRY(h, hipMemsetAsync(h->av_acc, 0, sizeof(double) * 9 * (size_t)h->ntotal, st));
   Aev64Params p{};
   const AevParams& r = h->ap_run;
   p.S = r.S; p.nR = r.nR; p.nA = r.nA; p.nZ = r.nZ; p.radial_len = r.radial_len; p.aev_len = r.aev_len; p.aev_stride = r.aev_stride;
@@ -1109,7 +1120,7 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
       launch_gemm64(g, EPI_PLAIN, st);
     }
   }
-  launch_aev64_backward(p, a, st);
+  launch_aev64_backward(p, a, st, static_cast<double*>(h->av_acc));
   if (m.has_rep) {
     HIP_TRY(h, h->erep.reserve(kVirialSlots));
     HIP_TRY(h, hipMemsetAsync(h->erep.p, 0, sizeof(double) * kVirialSlots, st));
@@ -1117,7 +1128,7 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
     ra.row_info = h->row_info.p; ra.nrows = h->nrows; ra.jlist = h->jlist.p; ra.species = h->species.p;
     ra.pos = d_x; ra.fbuf = h->fbuf64.p; ra.virial = vflag ? h->virial_acc.p : nullptr; ra.erep = h->erep.p;
     ra.tables = h->rep_tables.p; ra.S = m.S; ra.nslots = kVirialSlots; ra.vslots = 1; ra.cutoff = m.rep_cut;
-    launch_repulsion(ra, true, st);
+    launch_repulsion(ra, true, st, h->av_acc);
   }
   Sae64 sae{};
   for (int s = 0; s < m.S; s++) sae.v[s] = m.sae[s];
@@ -1240,13 +1251,14 @@ int step_backward(ani_handle* h, const StepCtx& c, const AevArgs& a, hipStream_t
         rt.k[8 * ca + cb] = (float)m.rep_tables[2 * n2 + src];
       }
   }
-  const bool rep_done = launch_aev_backward(h->ap_run, a, h->max_numneigh, st, rt.on ? &rt : nullptr) && rt.on;
+  float* avir = static_cast<float*>(h->av_acc);   // armed step: per-atom virial (ani_request_atom_virial)
+  const bool rep_done = launch_aev_backward(h->ap_run, a, h->max_numneigh, st, rt.on ? &rt : nullptr, avir) && rt.on;
   if (m.has_rep && !rep_done) {
     RepArgs ra{};
     ra.row_info = h->row_info.p; ra.nrows = h->nrows; ra.jlist = h->jlist.p; ra.species = h->species.p;
     ra.pos = c.d_x; ra.fbuf = h->fbuf.p; ra.virial = c.vflag ? h->virial_acc.p : nullptr; ra.erep = h->erep.p;
     ra.tables = h->rep_tables.p; ra.S = m.S; ra.nslots = kVirialSlots; ra.vslots = kVirialSlots; ra.cutoff = m.rep_cut;
-    launch_repulsion(ra, false, st);
+    launch_repulsion(ra, false, st, avir);
   }
   return ANI_OK;
 }
@@ -1281,6 +1293,7 @@ int run_step(ani_handle* h, const double* d_x, int eflag_atom, int vflag, double
   int rc = step_prologue(h, c, true, st);
   if (rc) return rc;
   step_pack(h, c, 0, h->ntotal, true, st);   // also clears fbuf / virial_acc / the energy word
+  if (h->av_acc) HIP_TRY(h, hipMemsetAsync(h->av_acc, 0, sizeof(float) * 9 * (size_t)h->ntotal, st));
   const AevArgs a = step_aev_args(h, c, 0);
   rc = step_compact_forward(h, a, st);
   if (rc) return rc;
@@ -1517,6 +1530,7 @@ void ani_destroy(ani_handle* h) {
   h->xyzs.release(); h->cl_xyz.release(); h->cl_hdr.release(); h->cl_j.release(); h->row_info.release(); h->row_flag.release(); h->row_list.release(); h->row_count.release(); h->x64.release(); h->f64.release(); h->ev.release(); h->eatom.release(); h->origin.release();
   h->rep_tables.release(); h->erep.release();
   h->nb_cell_id.release(); h->nb_cell_count.release(); h->nb_cell_start.release(); h->nb_cursor.release(); h->nb_order.release(); h->nb_xs.release();
+  h->avir.release(); h->avir64.release(); h->avout.release();
   h->virial_acc.release(); h->aev.release(); h->gaev.release(); h->act.release(); h->aev64.release(); h->gaev64.release(); h->act64.release(); h->e_rows64.release(); h->fbuf64.release(); h->e_rows.release(); h->fbuf.release();
   for (int fi = 0; fi < 4; fi++) free_fused(h, fi);
   h->fused_counter.release(); h->gaev_parts.release(); h->fused_sched.release();
@@ -1534,9 +1548,56 @@ int ani_aev_length(const ani_handle* h) { return h ? h->model.aev_len : 0; }
 double ani_cutoff_radial(const ani_handle* h) { return h ? h->model.Rcr : 0; }
 double ani_cutoff_angular(const ani_handle* h) { return h ? h->model.Rca : 0; }
 
+// ---- per-atom virial (ani_request_atom_virial) ----------------------------------------------------------------
+int ani_request_atom_virial(ani_handle* h, double* out, int ncomp) {
+  if (!h) return ANI_ERR_ARG;
+  h->av_out = nullptr;
+  h->av_ncomp = 0;
+  if (!out) return ANI_OK;
+  if (ncomp != 6 && ncomp != 9) {
+    h->err = "ani_request_atom_virial: ncomp must be 6 (vatom) or 9 (cvatom), got " + std::to_string(ncomp);
+    return ANI_ERR_ARG;
+  }
+  h->av_out = out;
+  h->av_ncomp = ncomp;
+  return ANI_OK;
+}
+
+// an entry point takes the arming (it holds for this one call); out == NULL: unarmed
+static double* take_atom_virial(ani_handle* h, int* ncomp) {
+  double* out = h ? h->av_out : nullptr;
+  *ncomp = h ? h->av_ncomp : 0;
+  if (h) { h->av_out = nullptr; h->av_ncomp = 0; }
+  return out;
+}
+
+// the accumulator of the step about to run (grown like the force buffers; cleared inside the step), or none
+static int atom_virial_begin(ani_handle* h, bool armed) {
+  h->av_acc = nullptr;
+  if (!armed) return ANI_OK;
+  const size_t n = (size_t)std::max(h->ntotal, 1) * 9;
+  if (h->use_single) {
+    HIP_TRY(h, h->avir.reserve(n));
+    h->av_acc = h->avir.p;
+  } else {
+    HIP_TRY(h, h->avir64.reserve(n));
+    h->av_acc = h->avir64.p;
+  }
+  return ANI_OK;
+}
+
+// accumulator -> d_out[rows][ncomp] (kcal/mol, LAMMPS order); a whole-step device call folds the images of an installed ghost fold
+static void atom_virial_out(ani_handle* h, double* d_out, int ncomp, int accumulate, bool fold, hipStream_t st) {
+  const bool f = fold && h->fold_nghost >= 0 && h->use_single;
+  launch_atom_virial(h->av_acc, !h->use_single, f ? h->nlocal : h->ntotal, ncomp, d_out, accumulate, f ? h->fold_head.p : nullptr,
+                     f ? h->fold_next.p : nullptr, h->nlocal, st);
+}
+
 int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_species, const double* d_x, int64_t npairs,
                             const int* d_ilist, const int* d_jlist, const int* d_numneigh, int ago, int eflag_atom, int vflag,
                             double* d_f, double* d_ev, double* d_eatom, void* stream) {
+  int av_ncomp = 0;
+  double* const av_out = take_atom_virial(h, &av_ncomp);
   int rc = check_args(h, ntotal, nlocal, npairs, ago);
   if (rc) return rc;
   if (!d_x || !d_ev) { h->err = "null device pointer"; return ANI_ERR_ARG; }
@@ -1566,7 +1627,11 @@ int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_
     if (rc) return rc;
     h->have_list = true;
   }
+  rc = atom_virial_begin(h, av_out != nullptr);
+  if (rc) return rc;
   rc = run_step(h, d_x, eflag_atom, vflag, d_f, /*accumulate=*/h->dev_overwrite ? 0 : 1, d_ev, d_eatom, st, /*fold=*/true);
+  if (rc == ANI_OK && av_out) atom_virial_out(h, av_out, av_ncomp, h->dev_overwrite ? 0 : 1, /*fold=*/true, st);
+  h->av_acc = nullptr;
   // LAMMPS_ANI_PROFILING (src/pair_ani_kokkos.cpp:68-70,210-212): the host's timers see the device work of this call
   if (rc == ANI_OK && h->profiling) HIP_TRY(h, hipStreamSynchronize(st));
   return rc;
@@ -1582,6 +1647,8 @@ static StepCtx split_ctx(const ani_handle* h) {
 
 int ani_step_begin(ani_handle* h, int ntotal, int nlocal, const double* d_x, int eflag_atom, int vflag, double* d_f, double* d_ev,
                    double* d_eatom, void* stream) {
+  int av_ncomp = 0;
+  double* const av_out = take_atom_virial(h, &av_ncomp);
   int rc = check_args(h, ntotal, nlocal, 0, /*ago=*/1);
   if (rc) return rc;
   if (!d_x || !d_ev) { h->err = "null device pointer"; return ANI_ERR_ARG; }
@@ -1589,6 +1656,11 @@ int ani_step_begin(ani_handle* h, int ntotal, int nlocal, const double* d_x, int
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   h->split.d_x = d_x; h->split.eflag_atom = eflag_atom; h->split.vflag = vflag; h->split.d_f = d_f; h->split.d_ev = d_ev; h->split.d_eatom = d_eatom;
+  // an armed split step: both backward halves add to one accumulator, ani_step_finish converts it
+  rc = atom_virial_begin(h, av_out != nullptr);
+  if (rc) return rc;
+  h->split_av = av_out;
+  h->split_av_ncomp = av_ncomp;
   h->split_phase = 1;
   if (!split_supported(h)) return ANI_OK;   // the whole step runs in ani_step_ghosts_ready
   rc = ensure_row_classes(h, st);
@@ -1598,6 +1670,7 @@ int ani_step_begin(ani_handle* h, int ntotal, int nlocal, const double* d_x, int
   rc = step_prologue(h, c, false, st);
   if (rc) { h->split_phase = 0; return rc; }
   step_pack(h, c, 0, h->nlocal, true, st);
+  if (h->av_acc) HIP_TRY(h, hipMemsetAsync(h->av_acc, 0, sizeof(float) * 9 * (size_t)h->ntotal, st));
   rc = step_compact_forward(h, step_aev_args(h, c, 2), st);
   if (rc) { h->split_phase = 0; return rc; }
   HIP_TRY(h, hipGetLastError());
@@ -1650,11 +1723,20 @@ int ani_step_finish(ani_handle* h, void* stream) {
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   h->split_phase = 0;
-  if (!split_supported(h)) return ANI_OK;
+  double* const av_out = h->split_av;
+  h->split_av = nullptr;
+  if (!split_supported(h)) {
+    if (av_out) atom_virial_out(h, av_out, h->split_av_ncomp, h->dev_overwrite ? 0 : 1, /*fold=*/false, st);
+    h->av_acc = nullptr;
+    HIP_TRY(h, hipGetLastError());
+    return ANI_OK;
+  }
   const StepCtx c = split_ctx(h);
   TraceRange tr("ani: step, finish");
   HIP_TRY(h, hipStreamWaitEvent(st, h->ev_side, 0));   // the backward pass launched by ani_step_ghosts_ready on the side stream
   step_finish(h, c, 0, h->nlocal, true, st);
+  if (av_out) atom_virial_out(h, av_out, h->split_av_ncomp, h->dev_overwrite ? 0 : 1, /*fold=*/false, st);
+  h->av_acc = nullptr;
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, take_launch_error());
   if (h->profiling) HIP_TRY(h, hipStreamSynchronize(st));
@@ -1815,9 +1897,17 @@ int ani_build_list(ani_handle* h, int ntotal, int nlocal, const int64_t* species
 int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* species, const double* coordinates, int64_t npairs,
                      const int* ilist_unique, const int* jlist, const int* numneigh, int ago, int eflag_atom, int vflag,
                      double* out_energy, double* out_force, double* out_atomic_energies, double* out_virial) {
+  int av_ncomp = 0;
+  double* const av_out = take_atom_virial(h, &av_ncomp);
   int rc = check_args(h, ntotal, nlocal, npairs, ago);
   if (rc) return rc;
   if (!coordinates || !out_force || !out_energy) { h->err = "null pointer argument"; return ANI_ERR_ARG; }
+  if (av_out && h->comm) {
+    // the ghost rows would have to go home through a 9-wide reverse exchange, which ani_comm does not have
+    h->err = "ani_request_atom_virial: the host entry points cannot return a per-atom virial with a communicator attached "
+             "(ani_attach_comm); detach it and reverse-communicate the ghost rows, or use ani_compute_full_device";
+    return ANI_ERR_ARG;
+  }
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
   if (h->comm && h->use_cuaev && !(h->ap.full_cap && h->ap_run.full_cap)) {
@@ -1861,8 +1951,19 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
   if (h->x64_from != coordinates)   // (a re-neighbouring step of the `devlist` mode: ani_build_list uploaded them a moment ago)
     HIP_TRY(h, hipMemcpyAsync(h->x64.p, coordinates, sizeof(double) * 3 * (size_t)ntotal, hipMemcpyHostToDevice, st));
   h->x64_from = nullptr;
-  rc = run_step(h, h->x64.p, eflag_atom, vflag, h->f64.p, /*accumulate=*/0, h->ev.p, h->eatom.p, st);
+  if (av_out) HIP_TRY(h, h->avout.reserve((size_t)std::max(ntotal, 1) * av_ncomp));
+  rc = atom_virial_begin(h, av_out != nullptr);
   if (rc) return rc;
+  // an armed step: every ntotal row of the per-atom virial is written, ghosts included (the caller folds them like the forces)
+  auto atom_virial_host = [&]() -> int {
+    if (!av_out) return ANI_OK;
+    atom_virial_out(h, h->avout.p, av_ncomp, /*accumulate=*/0, /*fold=*/false, st);
+    HIP_TRY(h, hipMemcpyAsync(av_out, h->avout.p, sizeof(double) * av_ncomp * (size_t)ntotal, hipMemcpyDeviceToHost, st));
+    return ANI_OK;
+  };
+  rc = run_step(h, h->x64.p, eflag_atom, vflag, h->f64.p, /*accumulate=*/0, h->ev.p, h->eatom.p, st);
+  if (!rc) rc = atom_virial_host();
+  if (rc) { h->av_acc = nullptr; return rc; }
   rc = finish_host(h, ntotal, nlocal, eflag_atom, vflag, out_energy, out_force, out_atomic_energies, out_virial);
   if (rc == ANI_ERR_CAPACITY && h->use_cuaev && !h->ap_run.full_cap && !h->comm) {
     // The screened radial lists are sized for 3/4 of the longest candidate list; a system denser than that inside Rcr
@@ -1874,9 +1975,12 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
     rc = rebuild(h, st);
     if (rc) return rc;
     rc = run_step(h, h->x64.p, eflag_atom, vflag, h->f64.p, /*accumulate=*/0, h->ev.p, h->eatom.p, st);
-    if (rc) return rc;
+    if (!rc) rc = atom_virial_host();
+    if (rc) { h->av_acc = nullptr; return rc; }
     rc = finish_host(h, ntotal, nlocal, eflag_atom, vflag, out_energy, out_force, out_atomic_energies, out_virial);
   }
+  h->av_acc = nullptr;
+  if (rc == ANI_OK && av_out) HIP_TRY(h, hipStreamSynchronize(st));
   return rc;
 }
 
@@ -1887,13 +1991,17 @@ int ani_compute_half(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
   // A half pair feeds both of its local ends (src/ani_csrc/ani.cpp:100-180: every atom < nlocal is a centre), so the
   // half list is expanded once per rebuild into the per-centre form the kernels consume.
   if (ago == 0) {
-    if (!atom_index12 && npairs_half > 0) { h->err = "null atom_index12 with ago == 0"; return ANI_ERR_ARG; }
+    if (!atom_index12 && npairs_half > 0) { h->err = "null atom_index12 with ago == 0"; h->av_out = nullptr; return ANI_ERR_ARG; }
     std::vector<int>& num = h->h_half_num;
     std::vector<int>& jl = h->h_half_j;
     num.assign(nlocal, 0);
     for (int64_t p = 0; p < npairs_half; p++) {
       const int64_t a = atom_index12[p], b = atom_index12[npairs_half + p];
-      if (a < 0 || a >= ntotal || b < 0 || b >= ntotal) { h->err = "atom_index12 entry out of range"; return ANI_ERR_ARG; }
+      if (a < 0 || a >= ntotal || b < 0 || b >= ntotal) {
+        h->err = "atom_index12 entry out of range";
+        h->av_out = nullptr;   // an armed call that fails still takes the arming
+        return ANI_ERR_ARG;
+      }
       if (a < nlocal) num[a]++;
       if (b < nlocal) num[b]++;
     }

@@ -267,7 +267,10 @@ struct RepTab {
                                 // from them (a float position in a 100 A box is 4e-6 A off, worth 4e-3 kcal/mol/A
                                 // of force on a bonded O-H pair)
 };
-bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep = nullptr);
+// avir: per-atom virial accumulator [ntotal][9] of an armed step (ani_request_atom_virial; floats, Hartree: avir[9 j + 3 a + b] +=
+// d_a g_b for every term whose force g lands on atom j, d = x_j - x_centre) -- NULL runs the unarmed kernels
+bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep = nullptr,
+                         float* avir = nullptr);
 bool aev_fast_path(const AevParams& p, int max_numneigh);
 // rebuild time: stable sort of every centre's neighbour segment by neighbour species (jin -> jout)
 void launch_sort_jlist(const int* d_species, const int* d_nbr_off, const int* d_numneigh, const int* d_jin, int* d_jout,
@@ -317,7 +320,8 @@ struct RepArgs {
   int S, nslots, vslots;  // slot counts are powers of two
   double cutoff;          // Angstrom
 };
-void launch_repulsion(const RepArgs& a, bool fp64, hipStream_t st);
+// avir: per-atom virial accumulator of an armed step, float (fp32 path) or double (fp64 path) [ntotal][9]; NULL: unarmed
+void launch_repulsion(const RepArgs& a, bool fp64, hipStream_t st, void* avir = nullptr);
 void launch_repulsion_energy(const double* erep, int nslots, double* d_ev, hipStream_t st);
 
 // energy reduction (+ self energies), per-centre energies, force conversion
@@ -342,6 +346,11 @@ struct FinishArgs {
   int fold_nlocal = 0;
 };
 void launch_finish(const FinishArgs& a, hipStream_t st);
+// per-atom virial of an armed step: accumulator [natoms (+ ghosts of a fold)][9] (float, or double with fp64) -> out[natoms][ncomp]
+// kcal/mol in LAMMPS order (ncomp 9: xx yy zz xy xz yz yx zx zy; 6: the symmetric part), added (accumulate) or written; fold_head:
+// the images of owned atom i are added into row i (natoms = nlocal then)
+void launch_atom_virial(const void* acc, bool fp64, int natoms, int ncomp, double* out, int accumulate, const int* fold_head,
+                        const int* fold_next, int fold_nlocal, hipStream_t st);
 
 // ---- double precision path (ani_kernels_f64.hip) ------------------------------------------------------------
 struct Aev64Params {
@@ -372,7 +381,7 @@ struct Gemm64Args {
 struct Sae64 { double v[kMaxSpecies]; };
 void launch_cvt_f32_f64(const float* src, double* dst, size_t n, hipStream_t st);
 void launch_aev64_forward(const Aev64Params& p, const Aev64Args& a, hipStream_t st);
-void launch_aev64_backward(const Aev64Params& p, const Aev64Args& a, hipStream_t st);
+void launch_aev64_backward(const Aev64Params& p, const Aev64Args& a, hipStream_t st, double* avir = nullptr);
 void launch_gemm64(const Gemm64Args& g, Epilogue epi, hipStream_t st);
 void launch_finish64(const double* e_rows, int M, int nrows, const int* centre_of_row, const int* ilist, const int* species,
                      const Sae64& sae, const double* fbuf, int ntotal, const double* vir, double* f_out, int accumulate, double* ev,

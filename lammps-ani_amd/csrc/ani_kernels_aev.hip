@@ -1203,10 +1203,26 @@ __device__ __forceinline__ void scatter_neighbours(const AevArgs& a, const T* g,
 #endif
 }
 
-template <int NA, int NZ, int NCH, int GR, bool VIR, typename PF>
+// Per-atom virial (ani_request_atom_virial): the same shape for the nine products of a scattered neighbour -- lane = (list slot,
+// component), an atom's nine adds leave from nine adjacent lanes of ONE instruction, seven atoms per instruction.
+// avir[9 j + 3 a + b] += d_a g_b with d = x_j - x_centre (float d[vs * q + a]) and g = dE_centre/dx_j: minus the site-energy
+// virial (x_j - x_i) (x) F_j^(i) in Hartree (the conversion kernel applies sign, units and component order)
+template <typename T, typename D>
+__device__ __forceinline__ void scatter_atom_virial(float* __restrict__ avir, const T* g, const D* d, int vs, const int* jx, int cnt,
+                                                    int lane) {
+  const int qs = lane / 9, k = lane - 9 * qs, ca = k / 3, cb = k - 3 * ca;
+  for (int base = 0; base < cnt; base += 7) {
+    const int q = base + qs;
+    if (qs < 7 && q < cnt) atomicAdd(&avir[9 * (long long)jx[q] + k], (float)d[vs * q + ca] * (float)g[3 * q + cb]);
+  }
+}
+
+// AV: per-atom virial into avir[ntotal][9] (see scatter_atom_virial); vt: [3*64] LDS staging of the radial-only displacements
+template <int NA, int NZ, int NCH, int GR, bool VIR, bool AV, typename PF>
 __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArgs& a, FastLds& L, int row, const hdr_t h,
                                                 const Loaded<NCH, true, GR> pf, int lane, float (&wv)[9],
-                                                const RepTab& rep, float& er, PF&& before_final_scatter BWD_STAMP_PARAMS) {
+                                                const RepTab& rep, float* __restrict__ avir, float* vt, float& er,
+                                                PF&& before_final_scatter BWD_STAMP_PARAMS) {
   constexpr int NR = 16;
   const int centre = h[0];
   const int nrad = hdr_nrad(h), nang = hdr_nang(h);
@@ -1242,6 +1258,7 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
   // to the force scatter.  A neighbour inside Rca parks its displacement, atom index and radial gradient in LDS, where
   // the angular stage adds to it. ----
   float fx = 0.f, fy = 0.f, fz = 0.f;   // this lane's share of sum_j g_j (force on the centre)
+  float ov[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // AV: the centre's own row, d (x) gs of the symmetric collection
   const float cR = -p.EtaR * kLog2e;
   const float rev = 0.5f * p.pi_over_Rcr * 0.3183098861837907f;
   const float revA = 0.5f * p.pi_over_Rca * 0.3183098861837907f;
@@ -1368,6 +1385,13 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
         }
       }
     }
+    if constexpr (AV) {
+      // the neighbour's term lands on the centre itself: (x_i - x_j) (x) gs in the centre's own row, from registers (gs = 0 unless
+      // sym); the neighbour's wave adds the mirror image to its row
+      ov[0] += v.x * gsx; ov[1] += v.x * gsy; ov[2] += v.x * gsz;
+      ov[3] += v.y * gsx; ov[4] += v.y * gsy; ov[5] += v.y * gsz;
+      ov[6] += v.z * gsx; ov[7] += v.z * gsy; ov[8] += v.z * gsz;
+    }
 #endif
     if (live && ang) {
       L.ad[t] = v;
@@ -1402,10 +1426,12 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
           const int q = lanes_below(mout);
           L.gt[3 * q] = gx; L.gt[3 * q + 1] = gy; L.gt[3 * q + 2] = gz;
           L.jt[q] = j;
+          if constexpr (AV) { vt[3 * q] = v.x; vt[3 * q + 1] = v.y; vt[3 * q + 2] = v.z; }
         }
       }
       wave_sync();
       scatter_neighbours(a, L.gt, L.jt, __popcll(mout), lane);
+      if constexpr (AV) scatter_atom_virial(avir, L.gt, vt, 3, L.jt, __popcll(mout), lane);
       wave_sync();   // the staging buffer is reused by the next chunk
     }
   }
@@ -1715,6 +1741,16 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
   }
   before_final_scatter();   // the caller's loads for the wave's next centre: in front of the atomics in the in-order memory queue
   scatter_neighbours(a, L.gd, L.aj, nang, lane);
+  if constexpr (AV) {
+    scatter_atom_virial(avir, L.gd, reinterpret_cast<const float*>(L.ad), 4, L.aj, nang, lane);
+    float mine = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      const float t = xor_sum<32>(xor_sum<16>(xor_sum<8>(xor_sum<4>(xor_sum<2>(xor_sum<1>(ov[k]))))));
+      if (lane == k) mine = t;
+    }
+    if (lane < 9) atomicAdd(&avir[9 * (long long)centre + lane], mine);
+  }
   fx = xor_sum<32>(xor_sum<16>(xor_sum<8>(xor_sum<4>(xor_sum<2>(xor_sum<1>(fx))))));
   fy = xor_sum<32>(xor_sum<16>(xor_sum<8>(xor_sum<4>(xor_sum<2>(xor_sum<1>(fy))))));
   fz = xor_sum<32>(xor_sum<16>(xor_sum<8>(xor_sum<4>(xor_sum<2>(xor_sum<1>(fz))))));
@@ -1723,11 +1759,25 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
   BWD_STAMP(5);   // final scatter
 }
 
-template <int NA, int NZ, int NCH, int GR, bool VIR>
-__global__ __launch_bounds__(64 * kWavesB, ANI_BWD_MINW) void aev_backward_fast(AevParams p, AevArgs a, int cap, int rowf, RepTab rep) {
+// LDS words per wave of the backward kernel: the armed instantiation (AV) stages the radial-only displacements behind the slice
+__host__ __device__ constexpr int bwd_wave_floats(int cap, int rowf, int S, bool av) {
+  return fast_wave_floats_row(cap, true, rowf, S) + (av ? 3 * 64 : 0);
+}
+static_assert((fast_wave_floats(0, true) + 3 * 64) * 4 * kWavesB <= 160 * 1024, "armed backward LDS");
+
+// AVP: empty, or float* for the armed instantiation (per-atom virial accumulator) -- a parameter pack, so that the unarmed kernels keep
+// their argument list, and with it their instruction stream, exactly as it was
+template <int NA, int NZ, int NCH, int GR, bool VIR, typename... AVP>
+__global__ __launch_bounds__(64 * kWavesB, ANI_BWD_MINW) void aev_backward_fast(AevParams p, AevArgs a, int cap, int rowf, RepTab rep,
+                                                                                AVP... avp) {
+  constexpr bool AV = sizeof...(AVP) > 0;
+  float* avir = nullptr;
+  if constexpr (AV) avir = (avp, ...);
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  FastLds L = carve<NA, NZ>(reinterpret_cast<float*>(smem4) + wave * fast_wave_floats_row(cap, true, rowf, p.S), cap, true, rowf);
+  float* wbase = reinterpret_cast<float*>(smem4) + wave * bwd_wave_floats(cap, rowf, p.S, AV);
+  FastLds L = carve<NA, NZ>(wbase, cap, true, rowf);
+  float* vt = AV ? wbase + fast_wave_floats_row(cap, true, rowf, p.S) : nullptr;
   float wv[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // this lane's share of the wave's virial
   float er = 0.f;                                                // ... and of its repulsion energy
 #ifdef ABLB_STAMPS
@@ -1746,7 +1796,7 @@ __global__ __launch_bounds__(64 * kWavesB, ANI_BWD_MINW) void aev_backward_fast(
 #else
     BWD_STAMP(1);
 #endif
-    backward_centre<NA, NZ, NCH, GR, VIR>(p, a, L, row, hc, cur, lane, wv, rep, er, [] {}, stamp_prev, stamp_acc);
+    backward_centre<NA, NZ, NCH, GR, VIR, AV>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, [] {}, stamp_prev, stamp_acc);
     stamp_acc[6] += 1;
   }
   if (wave == 0 && lane == 0) {
@@ -1782,7 +1832,7 @@ __global__ __launch_bounds__(64 * kWavesB, ANI_BWD_MINW) void aev_backward_fast(
     ANI_TICKET_TAKE(tk_k2)
     if (hc[0] >= 0 && in_range) {
       // header and lists go in by value: the hook overwrites hc / cur with the next centre's while this one finishes
-      backward_centre<NA, NZ, NCH, GR, VIR>(p, a, L, row, hc, cur, lane, wv, rep, er, [&]() {
+      backward_centre<NA, NZ, NCH, GR, VIR, AV>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, [&]() {
         const int kk1 = rank_of(k1);
         if (k1 < kstop && kk1 < a.kcount) {   // wave-uniform
           const int row1 = row_of(kk1);
@@ -1917,7 +1967,12 @@ __global__ __launch_bounds__(64 * kWaves) void aev_forward_generic(AevParams p, 
   for (int e = lane; e < p.aev_stride; e += 64) dst[e] = L.row[e];
 }
 
-__global__ __launch_bounds__(64 * kWaves) void aev_backward_generic(AevParams p, AevArgs a) {
+// AVP: empty, or float* for the armed instantiation: per-atom virial into avir[ntotal][9] (scatter_atom_virial's layout and sign)
+template <typename... AVP>
+__global__ __launch_bounds__(64 * kWaves) void aev_backward_generic(AevParams p, AevArgs a, AVP... avp) {
+  constexpr bool AV = sizeof...(AVP) > 0;
+  float* avir = nullptr;
+  if constexpr (AV) avir = (avp, ...);
   __shared__ WaveLds lds[kWaves];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * kWaves + wave;
@@ -2016,6 +2071,14 @@ __global__ __launch_bounds__(64 * kWaves) void aev_backward_generic(AevParams p,
       v[0] += gx * dx; v[1] += gx * dy; v[2] += gx * dz;
       v[3] += gy * dx; v[4] += gy * dy; v[5] += gy * dz;
       v[6] += gz * dx; v[7] += gz * dy; v[8] += gz * dz;
+    }
+  }
+  if constexpr (AV) {   // every term is scattered here: (slot, component) lanes, nine adjacent lanes per atom
+    const int qs = lane / 9, k = lane - 9 * qs, ca = k / 3, cb = k - 3 * ca;
+    const float* dv = ca == 0 ? L.dx : (ca == 1 ? L.dy : L.dz);
+    for (int base = 0; base < nrad; base += 7) {
+      const int q = base + qs;
+      if (qs < 7 && q < nrad) atomicAdd(&avir[9 * (long long)L.j[q] + k], dv[q] * L.gd[3 * q + cb]);
     }
   }
 #pragma unroll
@@ -2210,7 +2273,7 @@ bool launch_aev_forward_fused(const AevParams& p, const AevArgs& a, int max_numn
   return true;
 }
 
-bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep) {
+bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep, float* avir) {
   if (a.nrows <= 0) return true;
   RepTab rt{};
   if (rep) rt = *rep;
@@ -2219,12 +2282,14 @@ bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh,
     if (a.kcount <= 0) return true;
     const int cap = radial_cap(p, max_numneigh);
     const int rowf = (p.aev_stride + 63) / 64 * 64;
-    const size_t lds = (size_t)fast_wave_floats_row(cap, true, rowf, p.S) * 4 * kWavesB;
+    const size_t lds = (size_t)bwd_wave_floats(cap, rowf, p.S, avir != nullptr) * 4 * kWavesB;
     const bool k1 = fast_kind(p) == 1, n2 = !p.compat, g1 = p.aev_stride <= 256;
-#define ANI_BWD_CASE(NA, NZ, NCH, GR)                                                                   \
-  do {                                                                                                  \
-    if (a.virial) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true>, p, a, kWavesB, lds, cap, rowf, st, rt);  \
-    else launch_fast(aev_backward_fast<NA, NZ, NCH, GR, false>, p, a, kWavesB, lds, cap, rowf, st, rt);          \
+    // armed (per-atom virial): its own instantiations, always with the global virial; the unarmed kernels stay what they were
+#define ANI_BWD_CASE(NA, NZ, NCH, GR)                                                                              \
+  do {                                                                                                             \
+    if (avir) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true, float*>, p, a, kWavesB, lds, cap, rowf, st, rt, avir);  \
+    else if (a.virial) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true>, p, a, kWavesB, lds, cap, rowf, st, rt);      \
+    else launch_fast(aev_backward_fast<NA, NZ, NCH, GR, false>, p, a, kWavesB, lds, cap, rowf, st, rt);                   \
   } while (0)
     if (k1) {
       if (n2 && g1) ANI_BWD_CASE(8, 4, 1, 1);
@@ -2240,7 +2305,8 @@ bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh,
 #undef ANI_BWD_CASE
     return true;
   }
-  hipLaunchKernelGGL(aev_backward_generic, grid, block, 0, st, p, a);
+  if (avir) hipLaunchKernelGGL(aev_backward_generic<float*>, grid, block, 0, st, p, a, avir);
+  else hipLaunchKernelGGL(aev_backward_generic<>, grid, block, 0, st, p, a);
   return false;
 }
 

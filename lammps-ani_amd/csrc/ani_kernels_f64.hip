@@ -122,7 +122,13 @@ __global__ __launch_bounds__(64 * kW64) void aev64_forward(Aev64Params p, Aev64A
   for (int e = lane; e < p.aev_stride; e += 64) dst[e] = L.row[e];
 }
 
-__global__ __launch_bounds__(64 * kW64) void aev64_backward(Aev64Params p, Aev64Args a) {
+// AVP: empty, or double* for the armed instantiation: per-atom virial into avir[ntotal][9], avir[9 j + 3 a + b] += d_a g_b
+// (d = x_j - x_centre, g = dE_centre/dx_j), Hartree.  A parameter pack: the unarmed kernel keeps its argument list
+template <typename... AVP>
+__global__ __launch_bounds__(64 * kW64) void aev64_backward(Aev64Params p, Aev64Args a, AVP... avp) {
+  constexpr bool AV = sizeof...(AVP) > 0;
+  double* avir = nullptr;
+  if constexpr (AV) avir = (avp, ...);
   __shared__ Wave64 lds[kW64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * kW64 + wave;
@@ -210,6 +216,14 @@ __global__ __launch_bounds__(64 * kW64) void aev64_backward(Aev64Params p, Aev64
       v[0] += gx * dx; v[1] += gx * dy; v[2] += gx * dz;
       v[3] += gy * dx; v[4] += gy * dy; v[5] += gy * dz;
       v[6] += gz * dx; v[7] += gz * dy; v[8] += gz * dz;
+    }
+  }
+  if constexpr (AV) {   // (slot, component) lanes, nine adjacent lanes per atom
+    const int qs = lane / 9, k = lane - 9 * qs, ca = k / 3, cb = k - 3 * ca;
+    const double* dv = ca == 0 ? L.dx : (ca == 1 ? L.dy : L.dz);
+    for (int base = 0; base < nrad; base += 7) {
+      const int q = base + qs;
+      if (qs < 7 && q < nrad) atomicAdd(&avir[9 * (long long)L.j[q] + k], dv[q] * L.gd[3 * q + cb]);
     }
   }
   for (int off = 32; off > 0; off >>= 1) { fx += __shfl_xor(fx, off); fy += __shfl_xor(fy, off); fz += __shfl_xor(fz, off); }
@@ -340,9 +354,10 @@ void launch_aev64_forward(const Aev64Params& p, const Aev64Args& a, hipStream_t 
   if (a.nrows <= 0) return;
   hipLaunchKernelGGL(aev64_forward, dim3((a.nrows + kW64 - 1) / kW64), dim3(64 * kW64), 0, st, p, a);
 }
-void launch_aev64_backward(const Aev64Params& p, const Aev64Args& a, hipStream_t st) {
+void launch_aev64_backward(const Aev64Params& p, const Aev64Args& a, hipStream_t st, double* avir) {
   if (a.nrows <= 0) return;
-  hipLaunchKernelGGL(aev64_backward, dim3((a.nrows + kW64 - 1) / kW64), dim3(64 * kW64), 0, st, p, a);
+  if (avir) hipLaunchKernelGGL(aev64_backward<double*>, dim3((a.nrows + kW64 - 1) / kW64), dim3(64 * kW64), 0, st, p, a, avir);
+  else hipLaunchKernelGGL(aev64_backward<>, dim3((a.nrows + kW64 - 1) / kW64), dim3(64 * kW64), 0, st, p, a);
 }
 void launch_gemm64(const Gemm64Args& g, Epilogue epi, hipStream_t st) {
   if (g.rows <= 0 || g.N <= 0) return;

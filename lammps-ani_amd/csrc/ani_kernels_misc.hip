@@ -399,6 +399,50 @@ void launch_finish(const FinishArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(finish_kernel, dim3(blocks), dim3(256), 0, st, a);
 }
 
+// ---- per-atom virial (ani_request_atom_virial): accumulator -> the caller's rows, only on armed steps ------------------------
+// acc[9 i + 3 a + b] = sum d_a g_b (Hartree) over the terms whose force lands on atom i (d = x_i - x_centre, g = dE_centre/dx_i), so
+// the site-energy virial is W_ab = -acc[3 a + b].  Out: kcal/mol, LAMMPS order -- ncomp 9 (cvatom): xx yy zz xy xz yz yx zx zy;
+// ncomp 6 (vatom): xx yy zz xy xz yz of the symmetric part.  With a ghost fold the rows of an atom's images are added to its own
+// (the chain of finish_kernel) and only the nlocal owned rows are written.
+template <typename T>
+__global__ __launch_bounds__(256) void atom_virial_kernel(const T* __restrict__ acc, int natoms, int ncomp, double* __restrict__ out,
+                                                          int accumulate, const int* __restrict__ fold_head,
+                                                          const int* __restrict__ fold_next, int fold_nlocal) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms) return;
+  double s[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) s[k] = (double)acc[9 * (long long)i + k];
+  if (fold_head) {
+    for (int g = fold_head[i]; g >= 0; g = fold_next[g]) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) s[k] += (double)acc[9 * ((long long)fold_nlocal + g) + k];
+    }
+  }
+  constexpr double c = -627.5094738898777;
+  double w[9];
+  w[0] = s[0]; w[1] = s[4]; w[2] = s[8];
+  if (ncomp == 9) {
+    w[3] = s[1]; w[4] = s[2]; w[5] = s[5]; w[6] = s[3]; w[7] = s[6]; w[8] = s[7];
+  } else {
+    w[3] = 0.5 * (s[1] + s[3]); w[4] = 0.5 * (s[2] + s[6]); w[5] = 0.5 * (s[5] + s[7]);
+  }
+  double* o = out + (long long)ncomp * i;
+  for (int k = 0; k < ncomp; k++) o[k] = accumulate ? o[k] + c * w[k] : c * w[k];
+}
+
+void launch_atom_virial(const void* acc, bool fp64, int natoms, int ncomp, double* out, int accumulate, const int* fold_head,
+                        const int* fold_next, int fold_nlocal, hipStream_t st) {
+  if (natoms <= 0) return;
+  const dim3 grid((natoms + 255) / 256), block(256);
+  if (fp64)
+    hipLaunchKernelGGL(atom_virial_kernel<double>, grid, block, 0, st, (const double*)acc, natoms, ncomp, out, accumulate, fold_head,
+                       fold_next, fold_nlocal);
+  else
+    hipLaunchKernelGGL(atom_virial_kernel<float>, grid, block, 0, st, (const float*)acc, natoms, ncomp, out, accumulate, fold_head,
+                       fold_next, fold_nlocal);
+}
+
 // ---- rows with and without a ghost atom among their candidates (rebuild time) ---------------------------------
 // flag[row] = 1 if any entry of the row's list is a ghost (index >= nlocal); one wave per row
 __global__ __launch_bounds__(256) void classify_rows_kernel(const int4* __restrict__ row_info, const int* __restrict__ jlist, int nrows,

@@ -20,8 +20,14 @@ namespace {
 constexpr double kAng2Bohr = 1.8897261258369282;
 
 // F = float: force accumulators float4 {fx,fy,fz,-};  F = double: double[3].  Positions are the caller's fp64 array.
-template <typename F>
-__global__ __launch_bounds__(256) void repulsion_kernel(RepArgs a) {
+// AVP: empty, or F* for the armed instantiation: per-atom virial into avir[ntotal][9], avir[9 j + 3 a + b] += d_a g_b (Hartree); each
+// list entry carries half the pair term, so a pair of two centres splits it half / half.  A lane per entry and nine adds per lane:
+// only the shapes off the fast kernel (which folds the repulsion into its radial stage) take this kernel
+template <typename F, typename... AVP>
+__global__ __launch_bounds__(256) void repulsion_kernel(RepArgs a, AVP... avp) {
+  constexpr bool AV = sizeof...(AVP) > 0;
+  F* avir = nullptr;
+  if constexpr (AV) avir = (avp, ...);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= a.nrows) return;
@@ -78,6 +84,13 @@ __global__ __launch_bounds__(256) void repulsion_kernel(RepArgs a) {
       atomicAdd(fb + 0, -gk[0]); atomicAdd(fb + 1, -gk[1]); atomicAdd(fb + 2, -gk[2]);
     }
     fi[0] += gk[0]; fi[1] += gk[1]; fi[2] += gk[2];
+    if constexpr (AV) {
+      F* av = avir + 9 * (long long)j;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int l = 0; l < 3; l++) atomicAdd(av + 3 * k + l, (F)(d[k] * gk[l]));
+    }
     if (a.virial) {
 #pragma unroll
       for (int k = 0; k < 3; k++)
@@ -128,11 +141,16 @@ __global__ void repulsion_energy_kernel(const double* __restrict__ erep, int nsl
 
 }  // namespace
 
-void launch_repulsion(const RepArgs& a, bool fp64, hipStream_t st) {
+void launch_repulsion(const RepArgs& a, bool fp64, hipStream_t st, void* avir) {
   if (a.nrows <= 0) return;
   const dim3 grid((a.nrows + 3) / 4), block(256);
-  if (fp64) hipLaunchKernelGGL(repulsion_kernel<double>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(repulsion_kernel<float>, grid, block, 0, st, a);
+  if (fp64) {
+    if (avir) hipLaunchKernelGGL((repulsion_kernel<double, double*>), grid, block, 0, st, a, (double*)avir);
+    else hipLaunchKernelGGL(repulsion_kernel<double>, grid, block, 0, st, a);
+  } else {
+    if (avir) hipLaunchKernelGGL((repulsion_kernel<float, float*>), grid, block, 0, st, a, (float*)avir);
+    else hipLaunchKernelGGL(repulsion_kernel<float>, grid, block, 0, st, a);
+  }
 }
 
 void launch_repulsion_energy(const double* erep, int nslots, double* d_ev, hipStream_t st) {
