@@ -145,6 +145,40 @@ int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_
 int ani_request_atom_virial(ani_handle* h, double* out, int ncomp);
 
 /*
+ * Ensemble model deviation: the spread between the members of the ensemble, the trust signal of query-by-committee (torchani's
+ * energies_qbcs) and of DeePMD's model_devi.  Arms the NEXT call of ani_compute_full / ani_compute_half or of
+ * ani_compute_full_device only (an entry point that fails still takes the arming); all pointers NULL disarms.  Pointers are host
+ * memory for the host entry points, device memory (the handle's device) for the device entry point.  Every output is
+ * OVERWRITTEN.  Any pointer may be NULL (that output is not formed).
+ * Definitions.  M = ani_use_num_models(h), at least 2 (else ANI_ERR_ARG, the handle stays unarmed).  E_i^m: energy of local
+ * centre i under member m, self energy included (the mean over m is eatom[i]).  F_j^m = -d(sum_i E_i^m)/dx_j over the centres of
+ * this call, network part only: the repulsion of REPULXTB models is the same for every member and drops out of every deviation.
+ * Bars denote the mean over members.  kcal/mol and kcal/mol/A.  The normaliser is the population one, 1/M, everywhere: torchani's
+ * unbiased sigma is sigma * sqrt(M / (M - 1)).
+ *   member_energy   [M]               sum over local centres of E_i^m plus this call's repulsion energy; the mean over m is ev[0]
+ *                                     up to rounding.  Adds across ranks: sum over ranks, then rho = std(E^m) / sqrt(N) (QBC).
+ *   atom_energy_dev [nlocal]          sigma_E,i = sqrt((1/M) sum_m (E_i^m - mean E_i)^2), indexed like eatom.
+ *   member_dforce   [ntotal][M][3]    dF_j^m = F_j^m - mean F_j for every row; ghost rows hold the ghost's share, which the caller
+ *                                     folds into the owner like a force (dF is linear).  With a ghost fold installed
+ *                                     (ani_set_ghost_fold, device entry) the ghost rows go into their owners and are NOT written.
+ *   atom_force_dev  [nlocal]          d_j = sqrt((1/M) sum_m |dF_j^m|^2) AFTER the ghost rows are folded into their owners
+ *                                     (DeePMD's per-atom force deviation).
+ *   summary         [4]               {max d_j, min d_j, sum d_j, max sigma_E,i} over the local atoms (nlocal == 0: {0, inf, 0,
+ *                                     0}); ranks reduce them with max / min / sum / max.
+ * atom_force_dev and summary need folded rows: the call has no ghosts (ntotal == nlocal), or it is ani_compute_full_device with a
+ * ghost fold installed (fp32).  Otherwise, and for any force output (member_dforce, atom_force_dev, summary) of a host entry point
+ * with a communicator attached, the call returns ANI_ERR_ARG, naming the reason, before it enqueues any work.  ani_step_begin on an
+ * armed handle returns ANI_ERR_ARG (the split step cannot return a deviation).
+ * Cost.  member_energy / atom_energy_dev alone: one small kernel after the step, no extra backward pass.  Force outputs: every
+ * member's own dE/dAEV rows (the fused MLP runs (tile, member) items, also under option mlp_fused 3; the per-layer and fp64 paths add
+ * one product per member), then M more passes of the step's AEV backward kernel, each on dg_m = dE_m/dAEV - mean, into a scratch
+ * accumulator.  Both precisions.  The step's own outputs (energy, forces, virial, eatom, an atom virial armed on the same step)
+ * do not change; unarmed steps run exactly the kernels they ran before.
+ */
+int ani_request_model_deviation(ani_handle* h, double* member_energy, double* atom_energy_dev, double* member_dforce,
+                                double* atom_force_dev, double* summary);
+
+/*
  * Ghosts that are images of the rank's OWN atoms (one rank with periodic boundaries; the self-images of a rank whose brick spans
  * the box in some direction): their two exchanges of a step folded into the step's own first and last kernel.  With a fold
  * installed, ani_compute_full_device
@@ -265,6 +299,9 @@ const char* ani_last_mlp_kernel(const ani_handle* h);
 int ani_debug_get(ani_handle* h, ani_debug_view* out);
 /* out[c], c < aev_active_length: column of the model's full AEV that column c of d_aev holds */
 int ani_debug_colmap(ani_handle* h, int* out);
+/* the last force-armed model-deviation step's dg_m = dE_m/dAEV - mean (Hartree): member m's rows at d_parts + m * member_stride
+ * elements, rows and columns laid out like d_gaev; float on an fp32 handle, double on an fp64 one (valid until the next step) */
+int ani_debug_deviation_parts(ani_handle* h, const void** d_parts, int64_t* member_stride);
 
 /*
  * Options (take effect at the next call with ago == 0):

@@ -23,7 +23,7 @@ EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani
            "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_set_option", "ani_phase_timing", "ani_phase_times",
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
            "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
-           "ani_request_atom_virial"]
+           "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts"]
 # include/ani_comm.h: the device-side ghost exchange over RCCL
 COMM_EXPORTS = ["ani_comm_get_unique_id", "ani_comm_create", "ani_comm_create_local", "ani_comm_destroy", "ani_comm_last_error", "ani_comm_rank",
                 "ani_comm_size", "ani_comm_plan", "ani_comm_exchange_counts", "ani_comm_alltoallv", "ani_comm_set_epoch",
@@ -99,6 +99,8 @@ def lib():
         L.ani_set_ghost_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ani_stage_ghost_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.ani_request_atom_virial.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ani_request_model_deviation.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        L.ani_debug_deviation_parts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
         L.ani_host_register.argtypes = [C.c_void_p, C.c_size_t]
         L.ani_host_unregister.argtypes = [C.c_void_p]
         L.ani_last_mlp_kernel.restype = C.c_char_p
@@ -192,15 +194,45 @@ class ANI:
             out = out.ctypes.data
         self._check(self._lib.ani_request_atom_virial(self._h, out, int(ncomp)))
 
-    def compute(self, inp, ago: int = 0, eflag_atom: bool = True, vflag: bool = True, force_into=None, atom_virial: int = 0):
+    DEVIATION_KEYS = ("member_energy", "atom_energy_dev", "member_dforce", "atom_force_dev", "summary")
+
+    def request_model_deviation(self, member_energy=None, atom_energy_dev=None, member_dforce=None, atom_force_dev=None,
+                                summary=None):
+        """ani_request_model_deviation: arm the NEXT step's ensemble deviation (include/ani_hip.h).  Each output is a C-contiguous
+        float64 numpy array (host entry points) or a device address (device entry point); None leaves it out, all None disarms."""
+        ptrs = []
+        for a in (member_energy, atom_energy_dev, member_dforce, atom_force_dev, summary):
+            if isinstance(a, np.ndarray):
+                assert a.dtype == np.float64 and a.flags.c_contiguous
+                a = a.ctypes.data
+            ptrs.append(a)
+        self._check(self._lib.ani_request_model_deviation(self._h, *ptrs))
+
+    def debug_deviation_parts(self):
+        """(device address, member stride in elements) of the last force-armed step's dg_m rows (ani_debug_deviation_parts)."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._check(self._lib.ani_debug_deviation_parts(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def compute(self, inp, ago: int = 0, eflag_atom: bool = True, vflag: bool = True, force_into=None, atom_virial: int = 0,
+                deviation: bool = False):
         """Host-pointer entry points with a harness.RankInput (full or half list).  Returns a dict like the oracle's.
         force_into: a C-contiguous float64 [ntotal, 3] array handed over as out_force (option out_force_accumulate adds into it).
-        atom_virial: 6 or 9 adds "atom_virial" [ntotal, atom_virial] (kcal/mol, include/ani_hip.h), 0 = not asked for."""
+        atom_virial: 6 or 9 adds "atom_virial" [ntotal, atom_virial] (kcal/mol, include/ani_hip.h), 0 = not asked for.
+        deviation: adds "deviation", a dict of the ensemble deviation (include/ani_hip.h): member_energy [M], atom_energy_dev
+        [nlocal] and member_dforce [ntotal, M, 3] always, atom_force_dev [nlocal] and summary [4] when the input has no ghosts."""
         nt, nl = inp.ntotal, inp.nlocal
         av = None
         if atom_virial:
             av = np.full((nt, int(atom_virial)), np.nan)
             self.request_atom_virial(av, int(atom_virial))
+        dv = None
+        if deviation:
+            M = self.use_num_models
+            dv = dict(member_energy=np.full(M, np.nan), atom_energy_dev=np.full(nl, np.nan), member_dforce=np.full((nt, M, 3), np.nan))
+            if nt == nl:
+                dv.update(atom_force_dev=np.full(nl, np.nan), summary=np.full(4, np.nan))
+            self.request_model_deviation(**dv)
         species = np.ascontiguousarray(inp.species, dtype=np.int64)
         x = np.ascontiguousarray(inp.x, dtype=np.float64)
         e = np.zeros(1)
@@ -224,14 +256,19 @@ class ANI:
         out = dict(energy=float(e[0]), force=f, eatom=ea, virial=vir.reshape(3, 3))
         if av is not None:
             out["atom_virial"] = av
+        if dv is not None:
+            out["deviation"] = dv
         return out
 
     def compute_device(self, ntotal, nlocal, d_species, d_x, npairs, d_ilist, d_jlist, d_numneigh, ago, d_f, d_ev,
-                       d_eatom=None, eflag_atom=False, vflag=False, stream=None, d_atom_virial=None, ncomp=9):
+                       d_eatom=None, eflag_atom=False, vflag=False, stream=None, d_atom_virial=None, ncomp=9, d_deviation=None):
         """Device-resident step; arguments are raw device addresses (e.g. torch tensor .data_ptr()).  d_atom_virial: device
-        [ntotal, ncomp] float64 the per-atom virial is ADDED to (include/ani_hip.h), None = not asked for."""
+        [ntotal, ncomp] float64 the per-atom virial is ADDED to (include/ani_hip.h), None = not asked for.  d_deviation: a dict
+        of device addresses keyed like request_model_deviation's arguments, the ensemble deviation is written there."""
         if d_atom_virial is not None:
             self.request_atom_virial(d_atom_virial, ncomp)
+        if d_deviation is not None:
+            self.request_model_deviation(**d_deviation)
         rc = self._lib.ani_compute_full_device(self._h, ntotal, nlocal, d_species, d_x, npairs, d_ilist, d_jlist,
                                                d_numneigh, ago, int(eflag_atom), int(vflag), d_f, d_ev, d_eatom, stream)
         self._check(rc)

@@ -180,6 +180,19 @@ struct ani_handle {
   DevBuf<float> avir;      // [ntotal][9] accumulator (Hartree) of an armed fp32 step
   DevBuf<double> avir64;   // ... of an fp64 step
   DevBuf<double> avout;    // [ntotal][ncomp] the host entry points' result on the device
+  // ensemble model deviation (ani_request_model_deviation): dv_req is armed for the next step only; dv holds the device outputs of
+  // the step being run (all NULL on an unarmed step).  dv_force: the step runs the M extra backward passes; dv_dsq: d_j is formed
+  // (folded rows: a ghost fold, or no ghosts); dv_fold: the passes' ghost rows go home through the fold
+  struct DevOut { double *member_energy, *atom_energy_dev, *member_dforce, *atom_force_dev, *summary; };
+  DevOut dv_req{}, dv{};
+  bool dv_on = false, dv_force = false, dv_dsq = false, dv_fold = false;
+  DevBuf<double> gaev_parts64;   // fp64 armed steps: every member's dE/dAEV rows, then their deviations dg_m
+  DevBuf<float> dv_fbuf;         // [ntotal][4] force accumulator of a member's pass (fp32)
+  DevBuf<double> dv_fbuf64;      // [ntotal][3] ... (fp64)
+  DevBuf<double> dv_tmp;         // [3][nlocal]: sum over m of |dF|^2, sigma_E and d for the summary
+  DevBuf<double> dv_stage;       // the host entry points' outputs on the device
+  DevBuf<double> dv_part;        // [M][kDevEnergyParts] block partials of member_energy
+  DevBuf<unsigned> dv_ticket;    // the closing kernel's ticket (zero between launches)
   int nlocal = 0, ntotal = 0, nrows = 0;
   long long npairs = 0;
   int count[kMaxSpecies] = {0}, row_start[kMaxSpecies] = {0};
@@ -754,7 +767,7 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
   if (gen) {
     int tiles128 = 0;
     for (int s = 0; s < m.S; s++) tiles128 += round_up(h->count[s], kRowTile) / kRowTile;
-    const int items128 = tiles128 * (m.M > 1 && h->mlp_fused != 3 ? m.M : 1);
+    const int items128 = tiles128 * (m.M > 1 && (h->mlp_fused != 3 || h->dv_force) ? m.M : 1);
     // 64-row tiles only where they still fit one round (a tile of either form costs about the same time per row)
     const bool small = h->mlp_fused_rows == 64 || (h->mlp_fused_rows == 0 && 2 * items128 <= fused_num_cus() + fused_num_cus() / 8);
     sub = small ? 2 : 1;
@@ -796,6 +809,13 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
   // beyond 8 GB the members run in sequence instead.
   const size_t parts_bytes = (size_t)std::max(h->nrows, 1) * ka * sizeof(float) * m.M;
   G.member_items = (m.M > 1 && parts_bytes <= ((size_t)8 << 30) && h->mlp_fused != 3) ? 1 : 0;
+  if (h->dv_force) {   // a model-deviation step needs every member's rows: (tile, member) items whatever the option says
+    if (parts_bytes > ((size_t)8 << 30)) {
+      h->err = "ani_request_model_deviation: the per-member dE/dAEV rows of this step would take more than 8 GB";
+      return ANI_ERR_ARG;
+    }
+    G.member_items = 1;
+  }
   if (G.member_items) {
     const size_t per = (size_t)std::max(h->nrows, 1) * ka;
     HIP_TRY(h, h->gaev_parts.reserve(per * m.M));
@@ -897,7 +917,10 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
     HIP_TRY(h, launch_mlp_fused(G, arith, st));
     h->last_mlp_kernel = arith == MLP_F16X2 ? "mlp_fused<2>" : "mlp_fused<3>";
   }
-  if (G.member_items) launch_sum_parts(h->gaev_parts.p, G.part_stride, m.M, h->gaev.p, (long long)h->nrows * ka, st);
+  if (G.member_items && h->dv_force)
+    launch_dev_parts(h->gaev_parts.p, G.part_stride, m.M, h->gaev.p, (long long)h->nrows * ka, /*sum=*/1, st);
+  else if (G.member_items)
+    launch_sum_parts(h->gaev_parts.p, G.part_stride, m.M, h->gaev.p, (long long)h->nrows * ka, st);
   return ANI_OK;
 }
 
@@ -1044,9 +1067,76 @@ int compute_mlp(ani_handle* h, hipStream_t st) {
     for (size_t l = 0; l < layer_probs.size(); l++)
       launch_gemm_group(layer_probs[l].data(), (int)layer_probs[l].size(), (Epilogue)layer_epi[l], st, arith);
   }
+  if (h->dv_force && M > 1) {
+    // model-deviation step: every member's own dE/dAEV rows, G_1 of member a (columns a w[1]) times its slice of WT[0], then
+    // dg_m in place against the mean the product above wrote.  The split planes of WT[0] are blocked by 16 k: a member's slice
+    // is a whole number of blocks when w[1] is a multiple of 16, else the product runs in fp32.
+    const int ka = h->ap_run.aev_stride;
+    const size_t per = (size_t)std::max(h->nrows, 1) * ka;
+    HIP_TRY(h, h->gaev_parts.reserve(per * M, true));
+    bool planes = arith != MLP_FP32;
+    for (int s = 0; s < m.S; s++) planes = planes && (h->count[s] == 0 || h->nets[s].w[1] % 16 == 0);
+    probs.clear();
+    for (int s = 0; s < m.S; s++) {
+      if (h->count[s] == 0) continue;
+      const SpeciesNet& n = h->nets[s];
+      GemmArgs g = base_args(s);
+      g.A = h->Gbuf[s][1]; g.Amask = h->Hbuf[s][1]; g.lda = M * n.w[1]; g.sA = n.w[1]; g.K = n.w[1];
+      g.Bt = n.WT0c ? n.WT0c : n.WT[0]; g.ldb = M * n.w[1]; g.sB = n.w[1];
+      g.N = h->ap_run.aev_len;
+      if (planes) {
+        set_planes(g, n.WT0c ? n.sp[spi].WT0c : n.sp[spi].WT[0], 0, a_bwd, n.wscale[0]);
+        g.sBp = (long long)(n.w[1] / 16) * g.N * mlp_planes(arith) * 16;
+      }
+      g.C = h->gaev_parts.p + (size_t)h->row_start[s] * ka; g.ldc = ka; g.sC = (long long)per;
+      probs.push_back(g);
+    }
+    launch_gemm_group(probs.data(), (int)probs.size(), EPI_PLAIN, st, planes ? arith : MLP_FP32);
+    launch_dev_parts(h->gaev_parts.p, (long long)per, M, h->gaev.p, (long long)h->nrows * ka, /*sum=*/0, st);
+  }
   return ANI_OK;
 }
 
+
+// ---- ensemble model deviation of an armed step (ani_request_model_deviation) ------------------------------------
+// After the step's own kernels: on a force-armed step M passes of the step's backward kernel, pass(m, part_stride, acc) on dg_m into
+// the scratch accumulator acc (no virial, atom virial, repulsion or energy: the step's accumulators stay untouched), each followed
+// by the kernel that writes member m's rows and adds up |dF|^2; then the closing kernel (member energies, sigma_E, d) and the
+// summary.  An energy-only arming costs the closing kernel alone.
+template <typename Pass>
+int deviation_run(ani_handle* h, Pass&& pass, hipStream_t st) {
+  const HostModel& m = h->model;
+  const int M = m.M, nl = h->nlocal;
+  const bool fp64 = !h->use_single;
+  double* dsq = h->dv_dsq ? h->dv_tmp.p : nullptr;
+  double* sig = h->dv.summary ? h->dv_tmp.p + (size_t)nl : nullptr;
+  double* dd = h->dv.summary ? h->dv_tmp.p + 2 * (size_t)nl : nullptr;
+  if (h->dv_force) {
+    const long long per = (long long)std::max(h->nrows, 1) * h->ap_run.aev_stride;
+    void* acc = fp64 ? static_cast<void*>(h->dv_fbuf64.p) : static_cast<void*>(h->dv_fbuf.p);
+    HIP_TRY(h, hipMemsetAsync(acc, 0, (fp64 ? 3 * sizeof(double) : 4 * sizeof(float)) * (size_t)h->ntotal, st));
+    const bool fold = h->dv_fold;
+    for (int a = 0; a < M; a++) {
+      pass(a, per, acc);
+      launch_dev_member(acc, fp64, fold ? nl : h->ntotal, nl, a, M, h->dv.member_dforce, dsq, fold ? h->fold_head.p : nullptr,
+                        fold ? h->fold_next.p : nullptr, nl, st);
+    }
+  }
+  DevCloseArgs ca{};
+  ca.e_rows = fp64 ? static_cast<const void*>(h->e_rows64.p) : static_cast<const void*>(h->e_rows.p);
+  ca.M = M; ca.nrows = h->nrows; ca.nrows_ld = h->nrows; ca.nlocal = nl;
+  ca.centre_of_row = h->centre_of_row.p; ca.ilist = h->ilist.p; ca.species = h->species.p;
+  for (int s = 0; s < m.S; s++) ca.sae[s] = m.sae[s];
+  ca.erep = m.has_rep ? h->erep.p : nullptr; ca.nslots = kVirialSlots;
+  ca.dsq = dsq;
+  ca.member_energy = h->dv.member_energy; ca.atom_energy_dev = h->dv.atom_energy_dev;
+  ca.atom_force_dev = dsq ? h->dv.atom_force_dev : nullptr;
+  ca.sig = sig; ca.dd = dd;
+  ca.partials = h->dv_part.p; ca.ticket = h->dv_ticket.p;
+  launch_dev_close(ca, fp64, st);
+  if (h->dv.summary) launch_dev_summary(dd, sig, nl, h->dv.summary, st);
+  return ANI_OK;
+}
 
 // precision 'double': same pipeline on the fp64 kernels (ani_kernels_f64.hip)
 int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, double* d_f, int f_accumulate, double* d_ev,
@@ -1074,6 +1164,8 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
   a.err_flag = h->err_flag.p;
   launch_aev64_forward(p, a, st);
   const int ka = r.aev_stride;
+  const size_t per = (size_t)std::max(h->nrows, 1) * ka;   // model-deviation step: rows of a member in gaev_parts64
+  if (h->dv_force) HIP_TRY(h, h->gaev_parts64.reserve(per * M, true));
   for (int s = 0; s < m.S; s++) {
     if (h->count[s] == 0) continue;
     const SpeciesNet& n = h->nets[s];
@@ -1119,7 +1211,16 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
       g.C = h->gaev64.p + (size_t)r0 * ka; g.ldc = ka;
       launch_gemm64(g, EPI_PLAIN, st);
     }
+    if (h->dv_force) {   // every member's own rows: G_1 of member b (columns b w[1]) times its slice of WT[0]
+      Gemm64Args g = base();
+      g.A = h->Hbuf64[s][1]; g.lda = M * n.w[1]; g.sA = n.w[1]; g.K = n.w[1];
+      g.Bt = n.WT0c64 ? n.WT0c64 : n.WT64[0]; g.ldb = M * n.w[1]; g.sB = n.w[1];
+      g.N = r.aev_len;
+      g.C = h->gaev_parts64.p + (size_t)r0 * ka; g.ldc = ka; g.sC = (long long)per;
+      launch_gemm64(g, EPI_PLAIN, st);
+    }
   }
+  if (h->dv_force) launch_dev_parts64(h->gaev_parts64.p, (long long)per, M, h->gaev64.p, (long long)h->nrows * ka, st);
   launch_aev64_backward(p, a, st, static_cast<double*>(h->av_acc));
   if (m.has_rep) {
     HIP_TRY(h, h->erep.reserve(kVirialSlots));
@@ -1135,6 +1236,15 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
   launch_finish64(h->e_rows64.p, M, h->nrows, h->centre_of_row.p, h->ilist.p, h->species.p, sae, h->fbuf64.p, h->ntotal,
                   vflag ? h->virial_acc.p : nullptr, d_f, f_accumulate, d_ev, eflag_atom ? d_eatom : nullptr, h->err_flag.p, st);
   if (m.has_rep) launch_repulsion_energy(h->erep.p, kVirialSlots, d_ev, st);
+  if (h->dv_on) {
+    Aev64Args ad = a;
+    ad.virial = nullptr;
+    const int rcd = deviation_run(h, [&](int b, long long stride, void* acc) {
+      ad.gaev = h->gaev_parts64.p + b * stride; ad.fbuf = static_cast<double*>(acc);
+      launch_aev64_backward(p, ad, st);
+    }, st);
+    if (rcd) return rcd;
+  }
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, take_launch_error());
   return ANI_OK;
@@ -1309,6 +1419,15 @@ int run_step(ani_handle* h, const double* d_x, int eflag_atom, int vflag, double
   if (h->evt) HIP_TRY(h, hipEventRecord(h->evt[3], st));
   step_finish(h, c, 0, h->ntotal, true, st);
   if (h->evt) HIP_TRY(h, hipEventRecord(h->evt[4], st));
+  if (h->dv_on) {
+    AevArgs ad = a;
+    ad.virial = nullptr;
+    rc = deviation_run(h, [&](int b, long long stride, void* acc) {
+      ad.gaev = h->gaev_parts.p + b * stride; ad.fbuf = static_cast<float*>(acc);
+      launch_aev_backward(h->ap_run, ad, h->max_numneigh, st);
+    }, st);
+    if (rc) return rc;
+  }
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, take_launch_error());
   return ANI_OK;
@@ -1531,6 +1650,8 @@ void ani_destroy(ani_handle* h) {
   h->rep_tables.release(); h->erep.release();
   h->nb_cell_id.release(); h->nb_cell_count.release(); h->nb_cell_start.release(); h->nb_cursor.release(); h->nb_order.release(); h->nb_xs.release();
   h->avir.release(); h->avir64.release(); h->avout.release();
+  h->gaev_parts64.release(); h->dv_fbuf.release(); h->dv_fbuf64.release(); h->dv_tmp.release(); h->dv_stage.release();
+  h->dv_part.release(); h->dv_ticket.release();
   h->virial_acc.release(); h->aev.release(); h->gaev.release(); h->act.release(); h->aev64.release(); h->gaev64.release(); h->act64.release(); h->e_rows64.release(); h->fbuf64.release(); h->e_rows.release(); h->fbuf.release();
   for (int fi = 0; fi < 4; fi++) free_fused(h, fi);
   h->fused_counter.release(); h->gaev_parts.release(); h->fused_sched.release();
@@ -1593,14 +1714,115 @@ static void atom_virial_out(ani_handle* h, double* d_out, int ncomp, int accumul
                      f ? h->fold_next.p : nullptr, h->nlocal, st);
 }
 
+// ---- ensemble model deviation (ani_request_model_deviation) --------------------------------------------------------
+using DevOut = ani_handle::DevOut;
+static bool dv_any(const DevOut& d) { return d.member_energy || d.atom_energy_dev || d.member_dforce || d.atom_force_dev || d.summary; }
+static bool dv_force_outputs(const DevOut& d) { return d.member_dforce || d.atom_force_dev || d.summary; }
+static bool dv_folded_outputs(const DevOut& d) { return d.atom_force_dev || d.summary; }
+
+int ani_request_model_deviation(ani_handle* h, double* member_energy, double* atom_energy_dev, double* member_dforce,
+                                double* atom_force_dev, double* summary) {
+  if (!h) return ANI_ERR_ARG;
+  h->dv_req = DevOut{};
+  const DevOut d{member_energy, atom_energy_dev, member_dforce, atom_force_dev, summary};
+  if (!dv_any(d)) return ANI_OK;
+  if (h->model.M < 2) {
+    h->err = "ani_request_model_deviation: needs an ensemble of at least 2 members, the handle uses " + std::to_string(h->model.M);
+    return ANI_ERR_ARG;
+  }
+  h->dv_req = d;
+  return ANI_OK;
+}
+
+// an entry point takes the arming (it holds for this one call)
+static DevOut take_deviation(ani_handle* h) {
+  const DevOut d = h ? h->dv_req : DevOut{};
+  if (h) h->dv_req = DevOut{};
+  return d;
+}
+
+// the contract checks of an armed call, before it enqueues any work.  fold: the call will run with a ghost fold installed
+static int deviation_check(ani_handle* h, const DevOut& d, int ntotal, int nlocal, bool device, bool fold) {
+  if (!dv_any(d)) return ANI_OK;
+  if (!device && h->comm && dv_force_outputs(d)) {
+    h->err = "ani_request_model_deviation: the host entry points cannot return force deviations with a communicator attached "
+             "(ani_attach_comm): there is no 3M-wide reverse exchange; detach it or use ani_compute_full_device with a ghost fold";
+    return ANI_ERR_ARG;
+  }
+  if (dv_folded_outputs(d) && ntotal != nlocal && !(device && fold && h->use_single)) {
+    h->err = "ani_request_model_deviation: atom_force_dev and summary need the ghost rows folded into their owners; this call has "
+             "ghost atoms and no ghost fold (ani_set_ghost_fold: ani_compute_full_device, fp32)";
+    return ANI_ERR_ARG;
+  }
+  return ANI_OK;
+}
+
+// the armed step about to run: its device outputs and scratch (grown like the force buffers)
+static int deviation_begin(ani_handle* h, const DevOut& d, bool fold) {
+  h->dv = d;
+  h->dv_on = dv_any(d);
+  h->dv_force = dv_force_outputs(d);
+  h->dv_dsq = dv_folded_outputs(d);
+  h->dv_fold = fold && h->fold_nghost >= 0 && h->use_single;
+  if (!h->dv_on) return ANI_OK;
+  if (h->dv_force) {
+    if (h->use_single) HIP_TRY(h, h->dv_fbuf.reserve((size_t)std::max(h->ntotal, 1) * 4));
+    else HIP_TRY(h, h->dv_fbuf64.reserve((size_t)std::max(h->ntotal, 1) * 3));
+  }
+  if (h->dv_dsq) HIP_TRY(h, h->dv_tmp.reserve((size_t)std::max(h->nlocal, 1) * 3));
+  HIP_TRY(h, h->dv_part.reserve((size_t)h->model.M * kDevEnergyParts));
+  HIP_TRY(h, h->dv_ticket.reserve(1, true));
+  return ANI_OK;
+}
+
+static void deviation_end(ani_handle* h) {
+  h->dv = DevOut{};
+  h->dv_on = h->dv_force = h->dv_dsq = h->dv_fold = false;
+}
+
+// the host entry points: the outputs are staged on the device, then copied into the caller's arrays
+struct DevStage {
+  DevOut dev{};   // into dv_stage
+  size_t off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};
+};
+static int deviation_stage(ani_handle* h, const DevOut& d, int ntotal, int nlocal, DevStage* sg) {
+  if (!dv_any(d)) return ANI_OK;
+  const size_t M = (size_t)h->model.M;
+  const size_t len[5] = {M, (size_t)nlocal, (size_t)ntotal * M * 3, (size_t)nlocal, 4};
+  size_t tot = 0;
+  for (int k = 0; k < 5; k++) { sg->off[k] = tot; sg->len[k] = len[k]; tot += len[k]; }
+  HIP_TRY(h, h->dv_stage.reserve(tot));
+  double* b = h->dv_stage.p;
+  sg->dev.member_energy = d.member_energy ? b + sg->off[0] : nullptr;
+  sg->dev.atom_energy_dev = d.atom_energy_dev ? b + sg->off[1] : nullptr;
+  sg->dev.member_dforce = d.member_dforce ? b + sg->off[2] : nullptr;
+  sg->dev.atom_force_dev = d.atom_force_dev ? b + sg->off[3] : nullptr;
+  sg->dev.summary = d.summary ? b + sg->off[4] : nullptr;
+  return ANI_OK;
+}
+static int deviation_copy_home(ani_handle* h, const DevOut& d, const DevStage& sg, hipStream_t st) {
+  double* const host[5] = {d.member_energy, d.atom_energy_dev, d.member_dforce, d.atom_force_dev, d.summary};
+  for (int k = 0; k < 5; k++)
+    if (host[k] && sg.len[k])
+      HIP_TRY(h, hipMemcpyAsync(host[k], h->dv_stage.p + sg.off[k], sizeof(double) * sg.len[k], hipMemcpyDeviceToHost, st));
+  return ANI_OK;
+}
+
 int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_species, const double* d_x, int64_t npairs,
                             const int* d_ilist, const int* d_jlist, const int* d_numneigh, int ago, int eflag_atom, int vflag,
                             double* d_f, double* d_ev, double* d_eatom, void* stream) {
   int av_ncomp = 0;
   double* const av_out = take_atom_virial(h, &av_ncomp);
+  const DevOut dv = take_deviation(h);
   int rc = check_args(h, ntotal, nlocal, npairs, ago);
   if (rc) return rc;
   if (!d_x || !d_ev) { h->err = "null device pointer"; return ANI_ERR_ARG; }
+  {
+    // the fold this call runs with: a list of the call (ago == 0) drops the installed one and takes a staged one (rebuild)
+    const bool fold = ago == 0 ? (h->stage_nghost >= 0 && h->stage_owner && h->stage_nghost == ntotal - nlocal) : h->fold_nghost >= 0;
+    rc = deviation_check(h, dv, ntotal, nlocal, /*device=*/true, fold);
+    if (rc) return rc;
+  }
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default stream (what torch's default stream is)
   if (ago == 0) {
@@ -1629,9 +1851,12 @@ int ani_compute_full_device(ani_handle* h, int ntotal, int nlocal, const int* d_
   }
   rc = atom_virial_begin(h, av_out != nullptr);
   if (rc) return rc;
+  rc = deviation_begin(h, dv, /*fold=*/true);
+  if (rc) { deviation_end(h); return rc; }
   rc = run_step(h, d_x, eflag_atom, vflag, d_f, /*accumulate=*/h->dev_overwrite ? 0 : 1, d_ev, d_eatom, st, /*fold=*/true);
   if (rc == ANI_OK && av_out) atom_virial_out(h, av_out, av_ncomp, h->dev_overwrite ? 0 : 1, /*fold=*/true, st);
   h->av_acc = nullptr;
+  deviation_end(h);
   // LAMMPS_ANI_PROFILING (src/pair_ani_kokkos.cpp:68-70,210-212): the host's timers see the device work of this call
   if (rc == ANI_OK && h->profiling) HIP_TRY(h, hipStreamSynchronize(st));
   return rc;
@@ -1649,6 +1874,10 @@ int ani_step_begin(ani_handle* h, int ntotal, int nlocal, const double* d_x, int
                    double* d_eatom, void* stream) {
   int av_ncomp = 0;
   double* const av_out = take_atom_virial(h, &av_ncomp);
+  if (dv_any(take_deviation(h))) {
+    h->err = "ani_request_model_deviation: the split step (ani_step_begin) cannot return a model deviation; use a whole-step entry";
+    return ANI_ERR_ARG;
+  }
   int rc = check_args(h, ntotal, nlocal, 0, /*ago=*/1);
   if (rc) return rc;
   if (!d_x || !d_ev) { h->err = "null device pointer"; return ANI_ERR_ARG; }
@@ -1899,9 +2128,12 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
                      double* out_energy, double* out_force, double* out_atomic_energies, double* out_virial) {
   int av_ncomp = 0;
   double* const av_out = take_atom_virial(h, &av_ncomp);
+  const DevOut dv = take_deviation(h);
   int rc = check_args(h, ntotal, nlocal, npairs, ago);
   if (rc) return rc;
   if (!coordinates || !out_force || !out_energy) { h->err = "null pointer argument"; return ANI_ERR_ARG; }
+  rc = deviation_check(h, dv, ntotal, nlocal, /*device=*/false, /*fold=*/false);
+  if (rc) return rc;
   if (av_out && h->comm) {
     // the ghost rows would have to go home through a 9-wide reverse exchange, which ani_comm does not have
     h->err = "ani_request_atom_virial: the host entry points cannot return a per-atom virial with a communicator attached "
@@ -1954,6 +2186,10 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
   if (av_out) HIP_TRY(h, h->avout.reserve((size_t)std::max(ntotal, 1) * av_ncomp));
   rc = atom_virial_begin(h, av_out != nullptr);
   if (rc) return rc;
+  DevStage dvs;
+  rc = deviation_stage(h, dv, ntotal, nlocal, &dvs);
+  if (!rc) rc = deviation_begin(h, dvs.dev, /*fold=*/false);
+  if (rc) { deviation_end(h); return rc; }
   // an armed step: every ntotal row of the per-atom virial is written, ghosts included (the caller folds them like the forces)
   auto atom_virial_host = [&]() -> int {
     if (!av_out) return ANI_OK;
@@ -1963,7 +2199,8 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
   };
   rc = run_step(h, h->x64.p, eflag_atom, vflag, h->f64.p, /*accumulate=*/0, h->ev.p, h->eatom.p, st);
   if (!rc) rc = atom_virial_host();
-  if (rc) { h->av_acc = nullptr; return rc; }
+  if (!rc && h->dv_on) rc = deviation_copy_home(h, dv, dvs, st);
+  if (rc) { h->av_acc = nullptr; deviation_end(h); return rc; }
   rc = finish_host(h, ntotal, nlocal, eflag_atom, vflag, out_energy, out_force, out_atomic_energies, out_virial);
   if (rc == ANI_ERR_CAPACITY && h->use_cuaev && !h->ap_run.full_cap && !h->comm) {
     // The screened radial lists are sized for 3/4 of the longest candidate list; a system denser than that inside Rcr
@@ -1976,11 +2213,14 @@ int ani_compute_full(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
     if (rc) return rc;
     rc = run_step(h, h->x64.p, eflag_atom, vflag, h->f64.p, /*accumulate=*/0, h->ev.p, h->eatom.p, st);
     if (!rc) rc = atom_virial_host();
-    if (rc) { h->av_acc = nullptr; return rc; }
+    if (!rc && h->dv_on) rc = deviation_copy_home(h, dv, dvs, st);
+    if (rc) { h->av_acc = nullptr; deviation_end(h); return rc; }
     rc = finish_host(h, ntotal, nlocal, eflag_atom, vflag, out_energy, out_force, out_atomic_energies, out_virial);
   }
   h->av_acc = nullptr;
-  if (rc == ANI_OK && av_out) HIP_TRY(h, hipStreamSynchronize(st));
+  const bool dv_on = h->dv_on;
+  deviation_end(h);
+  if (rc == ANI_OK && (av_out || dv_on)) HIP_TRY(h, hipStreamSynchronize(st));
   return rc;
 }
 
@@ -1991,7 +2231,12 @@ int ani_compute_half(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
   // A half pair feeds both of its local ends (src/ani_csrc/ani.cpp:100-180: every atom < nlocal is a centre), so the
   // half list is expanded once per rebuild into the per-centre form the kernels consume.
   if (ago == 0) {
-    if (!atom_index12 && npairs_half > 0) { h->err = "null atom_index12 with ago == 0"; h->av_out = nullptr; return ANI_ERR_ARG; }
+    if (!atom_index12 && npairs_half > 0) {
+      h->err = "null atom_index12 with ago == 0";
+      h->av_out = nullptr;
+      h->dv_req = DevOut{};
+      return ANI_ERR_ARG;
+    }
     std::vector<int>& num = h->h_half_num;
     std::vector<int>& jl = h->h_half_j;
     num.assign(nlocal, 0);
@@ -2000,6 +2245,7 @@ int ani_compute_half(ani_handle* h, int ntotal, int nlocal, const int64_t* speci
       if (a < 0 || a >= ntotal || b < 0 || b >= ntotal) {
         h->err = "atom_index12 entry out of range";
         h->av_out = nullptr;   // an armed call that fails still takes the arming
+        h->dv_req = DevOut{};
         return ANI_ERR_ARG;
       }
       if (a < nlocal) num[a]++;
@@ -2091,6 +2337,13 @@ int ani_debug_get(ani_handle* h, ani_debug_view* out) {
   }
   out->error_flags = h->sticky_flags;
   for (int s = 0; s < kMaxSpecies && s < 16; s++) out->species_count[s] = h->count[s];
+  return ANI_OK;
+}
+
+int ani_debug_deviation_parts(ani_handle* h, const void** d_parts, int64_t* member_stride) {
+  if (!h || !d_parts || !member_stride) return ANI_ERR_ARG;
+  *d_parts = h->use_single ? static_cast<const void*>(h->gaev_parts.p) : static_cast<const void*>(h->gaev_parts64.p);
+  *member_stride = (int64_t)std::max(h->nrows, 1) * h->ap_run.aev_stride;
   return ANI_OK;
 }
 

@@ -352,6 +352,41 @@ void launch_finish(const FinishArgs& a, hipStream_t st);
 void launch_atom_virial(const void* acc, bool fp64, int natoms, int ncomp, double* out, int accumulate, const int* fold_head,
                         const int* fold_next, int fold_nlocal, hipStream_t st);
 
+// ---- ensemble model deviation (ani_request_model_deviation), armed steps only ---------------------------------------------
+// parts[m][n] hold every member's dE/dAEV rows, scaled by 1/M like the step's.  sum != 0: dst = sum over m of parts[m] in the order
+// of sum_parts_kernel (the step's own dE/dAEV, bit for bit); sum == 0: dst already holds the mean.  Then, in place,
+// parts[m] = M parts[m] - dst: the member's deviation dg_m from the mean.  fp32: n a multiple of 4.
+void launch_dev_parts(float* parts, long long part_stride, int M, float* dst, long long n, int sum, hipStream_t st);
+void launch_dev_parts64(double* parts, long long part_stride, int M, const double* dst, long long n, hipStream_t st);
+// after the backward pass of member m on dg_m: acc (force accumulator of the pass, Hartree/A; float {x,y,z,-} per atom, or double
+// {x,y,z}) -> dforce[row][M][3] member m (kcal/mol/A, or not written when NULL), rows [0, nrows_out); fold_head: the images of
+// owned atom i are added into row i (nrows_out = nlocal then).  dsq[i] (i < nlocal; NULL: not formed) = |dF_i^m|^2, added over m
+// (written at m == 0).  Every accumulator row the kernel read is cleared for the next member.
+void launch_dev_member(void* acc, bool fp64, int nrows_out, int nlocal, int m, int M, double* dforce, double* dsq, const int* fold_head,
+                       const int* fold_next, int fold_nlocal, hipStream_t st);
+constexpr int kDevEnergyParts = 32;   // blocks per member of the member-energy sums (launch_dev_close)
+struct DevCloseArgs {
+  const void* e_rows;        // [M][nrows_ld] per-member row energies scaled by 1/M (float, or double with fp64)
+  int M, nrows, nrows_ld, nlocal;
+  const int* centre_of_row;
+  const int* ilist;
+  const int* species;
+  double sae[kMaxSpecies];
+  const double* erep;        // [nslots] the step's repulsion energy partial sums (Hartree), or NULL
+  int nslots;
+  const double* dsq;         // [nlocal] sum over m of |dF_i^m|^2 (kcal/mol/A)^2, or NULL
+  double* member_energy;     // [M] kcal/mol, or NULL
+  double* atom_energy_dev;   // [nlocal] by centre, like eatom, or NULL
+  double* atom_force_dev;    // [nlocal], or NULL
+  double* sig;               // [nlocal] copies of sigma_E and d for the summary, or NULL
+  double* dd;
+  double* partials;          // [M][kDevEnergyParts] block partials of member_energy
+  unsigned* ticket;          // zero between launches (the last energy block resets it)
+};
+void launch_dev_close(const DevCloseArgs& a, bool fp64, hipStream_t st);
+// summary[4] = {max d, min d, sum d, max sigma_E} over [0, nlocal) (one block)
+void launch_dev_summary(const double* dd, const double* sig, int nlocal, double* summary, hipStream_t st);
+
 // ---- double precision path (ani_kernels_f64.hip) ------------------------------------------------------------
 struct Aev64Params {
   int S, nR, nA, nZ, radial_len, aev_len, aev_stride, compat;

@@ -443,6 +443,215 @@ void launch_atom_virial(const void* acc, bool fp64, int natoms, int ncomp, doubl
                        fold_next, fold_nlocal);
 }
 
+// ---- ensemble model deviation (ani_request_model_deviation): only on armed steps -----------------------------------------------
+// The armed replacement of sum_parts_kernel (ani_kernels_mlpf.hip): the mean in its order, then dg_m = M p_m - mean in place.
+__global__ __launch_bounds__(256) void dev_parts_kernel(float4* __restrict__ parts, long long stride4, int M, float4* __restrict__ dst,
+                                                        long long n4, int sum) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  float4 a;
+  if (sum) {
+    a = parts[i];
+    for (int m = 1; m < M; m++) {
+      const float4 b = parts[(long long)m * stride4 + i];
+      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    dst[i] = a;
+  } else {
+    a = dst[i];
+  }
+  const float fm = (float)M;
+  for (int m = 0; m < M; m++) {
+    float4 p = parts[(long long)m * stride4 + i];
+    p.x = fm * p.x - a.x; p.y = fm * p.y - a.y; p.z = fm * p.z - a.z; p.w = fm * p.w - a.w;
+    parts[(long long)m * stride4 + i] = p;
+  }
+}
+
+void launch_dev_parts(float* parts, long long part_stride, int M, float* dst, long long n, int sum, hipStream_t st) {
+  const long long n4 = n / 4;
+  if (n4 <= 0) return;
+  hipLaunchKernelGGL(dev_parts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<float4*>(parts),
+                     part_stride / 4, M, reinterpret_cast<float4*>(dst), n4, sum);
+}
+
+__global__ __launch_bounds__(256) void dev_parts64_kernel(double* __restrict__ parts, long long stride, int M,
+                                                          const double* __restrict__ dst, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = dst[i];
+  for (int m = 0; m < M; m++) parts[(long long)m * stride + i] = (double)M * parts[(long long)m * stride + i] - a;
+}
+
+void launch_dev_parts64(double* parts, long long part_stride, int M, const double* dst, long long n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(dev_parts64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parts, part_stride, M, dst, n);
+}
+
+// One thread per output row: the member's force deviation in kcal/mol/A (the conversion of finish_kernel), the images of a ghost
+// fold added in, |dF|^2 added up over the members, and the rows read cleared for the next member's pass (every image lies on
+// exactly one chain, so no row is read by two threads).
+template <typename T, int STRIDE>
+__global__ __launch_bounds__(256) void dev_member_kernel(T* __restrict__ acc, int nrows_out, int nlocal, int m, int M,
+                                                         double* __restrict__ dforce, double* __restrict__ dsq,
+                                                         const int* __restrict__ fold_head, const int* __restrict__ fold_next,
+                                                         int fold_nlocal) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrows_out) return;
+  T* r = acc + (long long)STRIDE * i;
+  double f[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    f[c] = (double)r[c];
+    r[c] = T(0);
+  }
+  if (fold_head) {
+    for (int g = fold_head[i]; g >= 0; g = fold_next[g]) {
+      T* q = acc + (long long)STRIDE * (fold_nlocal + g);
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        f[c] += (double)q[c];
+        q[c] = T(0);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) f[c] *= 627.5094738898777;
+  if (dforce) {
+    double* o = dforce + 3 * ((long long)i * M + m);
+    o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
+  }
+  if (dsq && i < nlocal) {
+    const double s = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
+    dsq[i] = m ? dsq[i] + s : s;
+  }
+}
+
+void launch_dev_member(void* acc, bool fp64, int nrows_out, int nlocal, int m, int M, double* dforce, double* dsq, const int* fold_head,
+                       const int* fold_next, int fold_nlocal, hipStream_t st) {
+  if (nrows_out <= 0) return;
+  const dim3 grid((nrows_out + 255) / 256), block(256);
+  if (fp64)
+    hipLaunchKernelGGL((dev_member_kernel<double, 3>), grid, block, 0, st, (double*)acc, nrows_out, nlocal, m, M, dforce, dsq, fold_head,
+                       fold_next, fold_nlocal);
+  else
+    hipLaunchKernelGGL((dev_member_kernel<float, 4>), grid, block, 0, st, (float*)acc, nrows_out, nlocal, m, M, dforce, dsq, fold_head,
+                       fold_next, fold_nlocal);
+}
+
+// Blocks [0, M kDevEnergyParts): member_energy in fp64 -- kDevEnergyParts blocks per member write block partials (fixed per-thread
+// order and tree); the last of them to finish (an integer ticket) adds them up in a fixed order: deterministic, no float atomics.
+// Then one thread per row: sigma_E of the row's centre.  Then one thread per owned atom: d = sqrt(dsq / M).
+template <typename T>
+__global__ __launch_bounds__(256) void dev_close_kernel(DevCloseArgs a, int energy_blocks, int row_blocks) {
+  const T* __restrict__ e = static_cast<const T*>(a.e_rows);
+  const double fm = (double)a.M, kcal = 627.5094738898777;
+  const int b = blockIdx.x;
+  if (b < energy_blocks) {
+    __shared__ double red[256];
+    __shared__ int last;
+    const int m = b / kDevEnergyParts, part = b - m * kDevEnergyParts;
+    double acc = 0.0;
+    for (int row = part * blockDim.x + threadIdx.x; row < a.nrows; row += kDevEnergyParts * blockDim.x) {
+      const int ii = a.centre_of_row[row];
+      if (ii < 0) continue;
+      acc += fm * (double)e[(long long)m * a.nrows_ld + row] + a.sae[a.species[a.ilist[ii]]];
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      a.partials[b] = red[0];
+      __threadfence();
+      last = atomicAdd(a.ticket, 1u) == (unsigned)energy_blocks - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double r = 0.0;   // the repulsion energy of the step, the same for every member
+    if (a.erep)
+      for (int s = threadIdx.x; s < a.nslots; s += blockDim.x) r += a.erep[s];
+    red[threadIdx.x] = r;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if ((int)threadIdx.x < a.M) {
+      const volatile double* pp = a.partials + (long long)threadIdx.x * kDevEnergyParts;
+      double t = 0.0;
+      for (int q = 0; q < kDevEnergyParts; q++) t += pp[q];
+      a.member_energy[threadIdx.x] = (t + red[0]) * kcal;
+    }
+    if (threadIdx.x == 0) *a.ticket = 0u;   // ready for the next launch
+    return;
+  }
+  if (b < energy_blocks + row_blocks) {
+    const int row = (b - energy_blocks) * blockDim.x + threadIdx.x;
+    if (row >= a.nrows) return;
+    const int ii = a.centre_of_row[row];
+    if (ii < 0) return;
+    double mean = 0.0;
+    for (int m = 0; m < a.M; m++) mean += (double)e[(long long)m * a.nrows_ld + row];
+    mean /= fm;
+    double v = 0.0;
+    for (int m = 0; m < a.M; m++) {
+      const double d = (double)e[(long long)m * a.nrows_ld + row] - mean;
+      v += d * d;
+    }
+    const double sig = fm * sqrt(v / fm) * kcal;   // the rows hold E / M
+    if (a.atom_energy_dev) a.atom_energy_dev[ii] = sig;
+    if (a.sig) a.sig[ii] = sig;
+    return;
+  }
+  const int i = (b - energy_blocks - row_blocks) * blockDim.x + threadIdx.x;
+  if (i >= a.nlocal) return;
+  const double d = sqrt(a.dsq[i] / fm);
+  if (a.atom_force_dev) a.atom_force_dev[i] = d;
+  if (a.dd) a.dd[i] = d;
+}
+
+void launch_dev_close(const DevCloseArgs& a, bool fp64, hipStream_t st) {
+  const int eb = a.member_energy ? a.M * kDevEnergyParts : 0;
+  const int rb = (a.atom_energy_dev || a.sig) ? (a.nrows + 255) / 256 : 0;
+  const int ab = a.dsq ? (a.nlocal + 255) / 256 : 0;
+  if (eb + rb + ab == 0) return;
+  if (fp64)
+    hipLaunchKernelGGL(dev_close_kernel<double>, dim3(eb + rb + ab), dim3(256), 0, st, a, eb, rb);
+  else
+    hipLaunchKernelGGL(dev_close_kernel<float>, dim3(eb + rb + ab), dim3(256), 0, st, a, eb, rb);
+}
+
+__global__ __launch_bounds__(1024) void dev_summary_kernel(const double* __restrict__ dd, const double* __restrict__ sig, int nlocal,
+                                                           double* __restrict__ summary) {
+  __shared__ double red[4][16];
+  double mx = 0.0, mn = HUGE_VAL, sm = 0.0, ms = 0.0;
+  for (int i = threadIdx.x; i < nlocal; i += blockDim.x) {
+    const double d = dd[i], s = sig[i];
+    mx = fmax(mx, d); mn = fmin(mn, d); sm += d; ms = fmax(ms, s);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = fmax(mx, __shfl_xor(mx, off)); mn = fmin(mn, __shfl_xor(mn, off));
+    sm += __shfl_xor(sm, off); ms = fmax(ms, __shfl_xor(ms, off));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if (lane == 0) { red[0][wave] = mx; red[1][wave] = mn; red[2][wave] = sm; red[3][wave] = ms; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < nw; w++) {
+      mx = fmax(mx, red[0][w]); mn = fmin(mn, red[1][w]); sm += red[2][w]; ms = fmax(ms, red[3][w]);
+    }
+    summary[0] = mx; summary[1] = mn; summary[2] = sm; summary[3] = ms;
+  }
+}
+
+void launch_dev_summary(const double* dd, const double* sig, int nlocal, double* summary, hipStream_t st) {
+  hipLaunchKernelGGL(dev_summary_kernel, dim3(1), dim3(1024), 0, st, dd, sig, nlocal, summary);
+}
+
 // ---- rows with and without a ghost atom among their candidates (rebuild time) ---------------------------------
 // flag[row] = 1 if any entry of the row's list is a ghost (index >= nlocal); one wave per row
 __global__ __launch_bounds__(256) void classify_rows_kernel(const int4* __restrict__ row_info, const int* __restrict__ jlist, int nrows,
