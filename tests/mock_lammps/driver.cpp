@@ -19,6 +19,7 @@ struct Session {
   std::vector<int> type, ilist, numneigh, jflat;
   std::vector<int*> firstneigh;
   NeighList list;
+  const int* next_ilist = nullptr;   // mock_set_ilist: the order of list.ilist at the next re-neighbouring call
   std::string err;
 };
 lammpsplugin_t g_plugin;
@@ -61,6 +62,12 @@ int mock_pair_style(void* h, int narg, const char** args, int ntypes) {
 int mock_last_request(void* h) { return ((Session*)h)->lmp.neighbor->last_request; }
 double mock_init_one(void* h) { return ((Session*)h)->pair->init_one(1, 1); }
 
+// The order of the centres for the NEXT mock_compute call with ago == 0 (that call only): list.ilist becomes ilist[0 .. nlocal),
+// a permutation of the owned atoms, while list.numneigh and list.firstneigh stay indexed by ATOM, as in LAMMPS (a binned
+// build after atom sorting, or a list copied from another request, does not hand the centres over as 0, 1, 2, ...).  The caller
+// keeps the array alive until that call; NULL takes the request back.
+void mock_set_ilist(void* h, const int* ilist) { ((Session*)h)->next_ilist = ilist; }
+
 // one Verlet-style force call: positions, types, full or half list (per-atom lists, possibly with special bits set)
 int mock_compute(void* h, int nlocal, int nghost, const double* x, const int* type, const int* numneigh, const int* jflat,
                  const int* owner, int ago, int eflag, int vflag, double* f_out, double* eng_vdwl, double* virial6, double* eatom_out) {
@@ -87,6 +94,10 @@ int mock_compute(void* h, int nlocal, int nghost, const double* x, const int* ty
       s->firstneigh.resize(nlocal);
       size_t off = 0;
       for (int i = 0; i < nlocal; i++) { s->ilist[i] = i; s->firstneigh[i] = s->jflat.data() + off; off += numneigh[i]; }
+      if (s->next_ilist) {
+        s->ilist.assign(s->next_ilist, s->next_ilist + nlocal);
+        s->next_ilist = nullptr;
+      }
       s->list.inum = nlocal; s->list.ilist = s->ilist.data(); s->list.numneigh = s->numneigh.data(); s->list.firstneigh = s->firstneigh.data();
       s->pair->list = &s->list;
       s->lmp.comm->owner.assign(owner, owner + nghost);

@@ -32,6 +32,7 @@ def mock():
     lib.mock_compute.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.mock_restart_roundtrip.argtypes = [C.c_void_p, C.c_char_p]
     lib.mock_destroy.argtypes = [C.c_void_p]
+    lib.mock_set_ilist.argtypes = [C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -105,6 +106,41 @@ def test_adapter_matches_golden_water30(mock, model_cache, nbr, aev):
     f2, e2, _, _ = _run(mock, h, inp, 0)
     np.testing.assert_allclose(f2, f, rtol=0, atol=1e-3)  # float atomics: not bitwise
     assert abs(e2 - e) < 1e-6
+    mock.mock_destroy(h)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", ["reversed", "random"])
+def test_adapter_with_an_ilist_that_is_not_the_identity(mock, model_cache, order):
+    """LAMMPS hands the centres over in list->ilist order, with numneigh / firstneigh indexed by ATOM.  The adapter gathers
+    numneigh[ilist[ii]] and firstneigh[ilist[ii]] into the library's ilist-ordered arrays and scatters the per-centre energies
+    back through ilist (the reference's "numneigh indexing wart", SURVEY.md section 7, only agrees with LAMMPS for the identity).
+    Full list, per-atom energies: forces, eng_vdwl, virial and eatom BY ATOM against the fp64 fixture, over a rebuild in that
+    order, a cached step, and a rebuild back in the identity order."""
+    g = load_golden("water30_pbc_ani2x_m8")
+    inp = golden_input(g, half=False)
+    p = golden_model_path(g, model_cache)
+    nl = inp.nlocal
+    ilist = np.arange(nl)[::-1] if order == "reversed" else np.random.default_rng(30).permutation(nl)
+    ilist = np.ascontiguousarray(ilist, dtype=np.int32)
+    assert np.array_equal(np.sort(ilist), np.arange(nl)) and int((ilist == np.arange(nl)).sum()) <= 2
+    eref = g["strict_eatom"]
+    assert np.abs(eref - eref[ilist]).max() > 1000 * 2e-3   # eatom left in ilist order would miss by the H / O self energies
+    h = mock.mock_create(b"real", 0)
+    rc, err = _style(mock, h, ["5.1", p, "hip", "-1", "cuaev", "full", "single"])
+    assert rc == 0, err
+    ref_f = g["strict_force"]
+    folded = ref_f[:nl].copy()
+    np.add.at(folded, inp.owner_lidx, ref_f[nl:])
+    vref = g["strict_virial"]
+    for ago, permuted in ((0, True), (1, True), (0, False)):
+        if ago == 0 and permuted:
+            mock.mock_set_ilist(h, ilist.ctypes.data)
+        f, e, v, ea = _run(mock, h, inp, ago)
+        assert abs(e - float(g["strict_energy"])) < 2e-3
+        np.testing.assert_allclose(f[:nl], folded, rtol=0, atol=2.3e-3)
+        np.testing.assert_allclose(v, [vref[0, 0], vref[1, 1], vref[2, 2], vref[0, 1], vref[0, 2], vref[1, 2]], rtol=0, atol=2e-2)
+        np.testing.assert_allclose(ea, eref, rtol=0, atol=2e-3)
     mock.mock_destroy(h)
 
 
