@@ -755,31 +755,30 @@ int ensure_fused(ani_handle* h, MlpArith arith, int gen, hipStream_t st) {
   return ANI_OK;
 }
 
-int compute_mlp_fused(ani_handle* h, hipStream_t st) {
+// The 16-row kernel: 128-row tiles on eight waves (two per SIMD) where that fills the CUs, else 64-row tiles on four -- twice
+// the workgroups, about half the latency of a tile (a decomposed box's per-GPU share: 12 501 water atoms are 99 tiles of 128).
+// Returns the 64-row tiles per 128-row tile: 2 or 1.
+int fused_sub_tiles(const ani_handle* h) {
   const HostModel& m = h->model;
-  const MlpArith arith = h->mlp_arith;
-  const int gen = h->mlp_fused_gen ? 1 : 0, pi = (arith == MLP_F16X2 ? 1 : 0) + 2 * gen;
-  int rc = ensure_fused(h, arith, gen, st);
-  if (rc) return rc;
-  // The 16-row kernel: 128-row tiles on eight waves (two per SIMD) where that fills the CUs, else 64-row tiles on four -- twice
-  // the workgroups, about half the latency of a tile (a decomposed box's per-GPU share: 12 501 water atoms are 99 tiles of 128).
-  int sub = 1;   // 64-row tiles per 128-row tile
-  if (gen) {
-    int tiles128 = 0;
-    for (int s = 0; s < m.S; s++) tiles128 += round_up(h->count[s], kRowTile) / kRowTile;
-    const int items128 = tiles128 * (m.M > 1 && (h->mlp_fused != 3 || h->dv_force) ? m.M : 1);
-    // 64-row tiles only where they still fit one round (a tile of either form costs about the same time per row)
-    const bool small = h->mlp_fused_rows == 64 || (h->mlp_fused_rows == 0 && 2 * items128 <= fused_num_cus() + fused_num_cus() / 8);
-    sub = small ? 2 : 1;
-  }
+  if (!h->mlp_fused_gen) return 1;
+  int tiles128 = 0;
+  for (int s = 0; s < m.S; s++) tiles128 += round_up(h->count[s], kRowTile) / kRowTile;
+  const int items128 = tiles128 * (m.M > 1 && (h->mlp_fused != 3 || h->dv_force) ? m.M : 1);
+  // 64-row tiles only where they still fit one round (a tile of either form costs about the same time per row)
+  const bool small = h->mlp_fused_rows == 64 || (h->mlp_fused_rows == 0 && 2 * items128 <= device_num_cus() + device_num_cus() / 8);
+  return small ? 2 : 1;
+}
+
+// the launch's arguments but for the schedule: the problems (species buckets, costliest first), tile_start, member_items, gaev_parts
+int fill_fused_args(ani_handle* h, int fi, int sub, FusedArgs& G) {
+  const HostModel& m = h->model;
   HIP_TRY(h, h->fused_counter.reserve(1));
-  FusedArgs G{};
   G.M = m.M; G.alpha = (float)m.alpha; G.inv_alpha = (float)(1.0 / m.alpha); G.scale = 1.f / (float)m.M;
   G.counter = h->fused_counter.p;
   G.err_flag = h->err_flag.p;
   const int acols = h->ap_run.aev_len, ka = h->ap_run.aev_stride;
   int np = 0, total = 0;
-  for (int shape = 0; shape < 3; shape++)        // costliest species first
+  for (int shape = 0; shape < kNumFusedShapes; shape++)        // costliest species first
     for (int s = 0; s < m.S; s++) {
       const SpeciesNet& n = h->nets[s];
       if (h->count[s] == 0 || n.fused_shape != shape) continue;
@@ -790,12 +789,12 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
       p.gaev_row0 = h->row_start[s];
       p.e_rows = h->e_rows.p + h->row_start[s];
       p.centre_of_row = h->centre_of_row.p + h->row_start[s];
-      p.stream = n.fu[pi].stream; p.consts = n.fu[pi].consts;
+      p.stream = n.fu[fi].stream; p.consts = n.fu[fi].consts;
       p.sE = h->nrows;
       p.tiles = sub * (round_up(h->count[s], kRowTile) / kRowTile);
       p.shape = shape;
       p.ks0 = acols / 16; p.nt0 = (acols + 31) / 32; p.acols = acols; p.aev_stride = ka;
-      p.pieces_per_member = (int)n.fu[pi].ppm; p.consts_per_member = n.fu[pi].cpm;
+      p.pieces_per_member = (int)n.fu[fi].ppm; p.consts_per_member = n.fu[fi].cpm;
       G.tile_start[np] = total;
       total += p.tiles;
       np++;
@@ -822,94 +821,117 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
     G.gaev_parts = h->gaev_parts.p;
     G.part_stride = (long long)per;
   }
-  // which workgroup runs which items: a static schedule, remade when the tile counts change (re-neighbouring)
-  if (h->mlp_fused_sched) {
-    const int per_tile = G.member_items ? m.M : 1, bins = fused_num_cus();
-    const int nitems = total * per_tile;
-    int mix = np;   // the tile counts and shapes of the problems, folded into one word
-    for (int q = 0; q < np; q++) mix = mix * 1000003 + G.p[q].tiles * 4 + G.p[q].shape;
-    mix = mix * 31 + sub + 2 * gen + 4 * h->mlp_fused_halves;
-    if (h->sched_key[0] != total || h->sched_key[1] != per_tile || h->sched_key[2] != mix || h->sched_key[3] != bins || !h->fused_sched.p) {
-      // item types: one per problem; a (tile, member) item costs what its tile's member costs.  Item t of the kernel's numbering
-      // is tile t / per_tile: the items of a problem are contiguous.
-      int cnt[kMaxProblems];
-      double cost[kMaxProblems];
-      for (int q = 0; q < np; q++) {
-        int nt[3];
-        fused_shape_tiles(G.p[q].shape, nt);
-        cnt[q] = G.p[q].tiles * per_tile;
-        cost[q] = (double)G.p[q].ks0 * nt[0] + 4.0 * nt[0] * nt[1] + 4.0 * nt[1] * nt[2] + 2.0 * nt[0] * G.p[q].nt0 +
-                  12.0;   // MFMA blocks of a member + a little for what a tile costs whatever its size
-        if (!G.member_items) cost[q] *= m.M;
-      }
-      // The sixteen-row kernel takes half items: the schedule may cut the items of a last, mostly idle round in two.  A half costs
-      // about kFusedHalfCost of its item (64 of 128 rows with all the weights streamed: profiles/r04_mlp_halves.log), and the
-      // cost model is good to about 5 %: a split the model likes by at least 3 % is TIMED against the whole items on this very
-      // step's rows (three launches each, the first not counted; the launch is idempotent) and kept only if it is faster --
-      // once per set of tile counts (ANI_FUSED_AUTOTUNE=0: no timing, a split needs 8 % by the model).
-      std::vector<int> items((size_t)2 * std::max(nitems, 1)), off(bins + 1);
-      int nsched = nitems;
-      const int split_mode = !gen ? 0 : (h->mlp_fused_halves == 2 ? 2 : (sub != 2 ? h->mlp_fused_halves : 0));   // searched for 128-row tiles only
-      static const double half_cost = [] { const char* e = getenv("ANI_FUSED_HALF_COST"); return e ? atof(e) : kFusedHalfCost; }();
-      static const bool autotune = [] { const char* e = getenv("ANI_FUSED_AUTOTUNE"); return !(e && atoi(e) == 0); }();
-      auto upload = [&](const std::vector<int>& it, int n) -> int {
-        HIP_TRY(h, h->fused_sched.reserve((size_t)2 * std::max(nitems, 1) + bins + 1));
-        HIP_TRY(h, hipMemcpyAsync(h->fused_sched.p, it.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(h->fused_sched.p + n, off.data(), sizeof(int) * (size_t)(bins + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));   // items / off are locals; once per re-neighbouring
-        h->sched_nitems = n;
-        return ANI_OK;
-      };
-      auto timed = [&](float* ms) -> int {   // the fused launch with the schedule just uploaded
-        G.sched_items = h->fused_sched.p; G.sched_off = h->fused_sched.p + h->sched_nitems; G.sched_blocks = bins;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIP_TRY(h, hipEventCreate(&e0));
-        HIP_TRY(h, hipEventCreate(&e1));
-        hipError_t err = launch_mlp_fused16(G, arith, 8, st);
-        if (err == hipSuccess) err = hipEventRecord(e0, st);
-        for (int k = 0; k < 2 && err == hipSuccess; k++) err = launch_mlp_fused16(G, arith, 8, st);
-        if (err == hipSuccess) err = hipEventRecord(e1, st);
-        if (err == hipSuccess) err = hipEventSynchronize(e1);
-        if (err == hipSuccess) err = hipEventElapsedTime(ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        HIP_TRY(h, err);
-        return ANI_OK;
-      };
-      std::vector<int> split(np, 0);
-      (void)fused_schedule_halves(np, cnt, cost, half_cost, bins, split_mode, split.data(), items.data(), off.data(), &nsched,
-                                  autotune && split_mode == 1 ? 0.03 : 0.08);
-      int any_split = 0;
-      for (int q = 0; q < np; q++) any_split += split[q];
-      {
-        const int rcu = upload(items, nsched);
-        if (rcu) return rcu;
-      }
-      if (autotune && split_mode == 1 && any_split && !getenv("ANI_FUSED_SPLIT")) {
-        float t_split = 0.f, t_whole = 0.f;
-        int rct = timed(&t_split);
-        if (rct) return rct;
-        std::vector<int> items_w((size_t)std::max(nitems, 1)), off_split = off;
-        int n_w = nitems;
-        (void)fused_schedule_halves(np, cnt, cost, half_cost, bins, 0, nullptr, items_w.data(), off.data(), &n_w);
-        rct = upload(items_w, n_w);
-        if (!rct) rct = timed(&t_whole);
-        if (rct) return rct;
-        if (t_split < t_whole) {   // the split stays: back it goes
-          off = off_split;
-          rct = upload(items, nsched);
-          if (rct) return rct;
-        }
-        if (getenv("ANI_FUSED_AUTOTUNE_VERBOSE"))
-          fprintf(stderr, "libani_hip: fused MLP schedule, %d items: whole %.4f ms, with half items %.4f ms per launch -> %s\n", nitems,
-                  t_whole / 2, t_split / 2, t_split < t_whole ? "halves" : "whole");
-      }
-      h->sched_key[0] = total; h->sched_key[1] = per_tile; h->sched_key[2] = mix; h->sched_key[3] = bins;
-    }
-    G.sched_items = h->fused_sched.p;
-    G.sched_off = h->fused_sched.p + h->sched_nitems;
-    G.sched_blocks = bins;
+  return ANI_OK;
+}
+
+// ANI_FUSED_SPLIT (experiments): "k0,k1,..." = how many of each type's last items the schedule cuts in two, types not named
+// keep 0.  Returns split (filled), or null when the variable is not set.
+const int* forced_fused_split(const char* env, int ntypes, const int* count, int* split) {
+  if (!env) return nullptr;
+  std::fill(split, split + ntypes, 0);
+  int j = 0;
+  for (const char* q = env; *q && j < ntypes; j++) {
+    split[j] = std::max(0, std::min(count[j], atoi(q)));
+    while (*q && *q != ',') q++;
+    if (*q == ',') q++;
   }
+  return split;
+}
+
+// a schedule (n items, then bins + 1 offsets) -> h->fused_sched
+int upload_fused_schedule(ani_handle* h, const std::vector<int>& items, int n, const std::vector<int>& off, size_t cap, hipStream_t st) {
+  HIP_TRY(h, h->fused_sched.reserve(cap));
+  HIP_TRY(h, hipMemcpyAsync(h->fused_sched.p, items.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_TRY(h, hipMemcpyAsync(h->fused_sched.p + n, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(h, hipStreamSynchronize(st));   // items / off are the caller's locals; once per re-neighbouring
+  h->sched_nitems = n;
+  return ANI_OK;
+}
+
+// ms of two launches of the sixteen-row kernel on 128-row tiles with the schedule in h->fused_sched (a first one is not counted)
+int time_fused_schedule(ani_handle* h, FusedArgs& G, MlpArith arith, int bins, hipStream_t st, float* ms) {
+  G.sched_items = h->fused_sched.p; G.sched_off = h->fused_sched.p + h->sched_nitems; G.sched_blocks = bins;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIP_TRY(h, hipEventCreate(&e0));
+  HIP_TRY(h, hipEventCreate(&e1));
+  hipError_t err = launch_mlp_fused16(G, arith, 8, st);
+  if (err == hipSuccess) err = hipEventRecord(e0, st);
+  for (int k = 0; k < 2 && err == hipSuccess; k++) err = launch_mlp_fused16(G, arith, 8, st);
+  if (err == hipSuccess) err = hipEventRecord(e1, st);
+  if (err == hipSuccess) err = hipEventSynchronize(e1);
+  if (err == hipSuccess) err = hipEventElapsedTime(ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  HIP_TRY(h, err);
+  return ANI_OK;
+}
+
+// Which workgroup runs which items: a static schedule in h->fused_sched, remade when the tile counts change (re-neighbouring);
+// G.sched_* are pointed at it.
+int ensure_fused_schedule(ani_handle* h, FusedArgs& G, MlpArith arith, int gen, int sub, hipStream_t st) {
+  static const double half_cost = [] { const char* e = getenv("ANI_FUSED_HALF_COST"); return e ? atof(e) : kFusedHalfCost; }();
+  static const bool autotune = [] { const char* e = getenv("ANI_FUSED_AUTOTUNE"); return !(e && atoi(e) == 0); }();
+  const bool verbose = getenv("ANI_FUSED_AUTOTUNE_VERBOSE") != nullptr;
+  const char* split_env = getenv("ANI_FUSED_SPLIT");
+  const int np = G.nprob, total = G.tile_start[np], per_tile = G.member_items ? G.M : 1, bins = device_num_cus();
+  const int nitems = total * per_tile;
+  int mix = np;   // the tile counts and shapes of the problems, folded into one word
+  for (int q = 0; q < np; q++) mix = mix * 1000003 + G.p[q].tiles * 4 + G.p[q].shape;
+  mix = mix * 31 + sub + 2 * gen + 4 * h->mlp_fused_halves;
+  if (h->sched_key[0] != total || h->sched_key[1] != per_tile || h->sched_key[2] != mix || h->sched_key[3] != bins || !h->fused_sched.p) {
+    // item types: one per problem; a (tile, member) item costs what its tile's member costs.  Item t of the kernel's numbering
+    // is tile t / per_tile: the items of a problem are contiguous.
+    int cnt[kMaxProblems], forced[kMaxProblems];
+    double cost[kMaxProblems];
+    for (int q = 0; q < np; q++) {
+      int nt[3];
+      fused_shape_tiles(G.p[q].shape, nt);
+      cnt[q] = G.p[q].tiles * per_tile;
+      cost[q] = (double)G.p[q].ks0 * nt[0] + 4.0 * nt[0] * nt[1] + 4.0 * nt[1] * nt[2] + 2.0 * nt[0] * G.p[q].nt0 +
+                12.0;   // MFMA blocks of a member + a little for what a tile costs whatever its size
+      if (!G.member_items) cost[q] *= G.M;
+    }
+    const int* forced_split = forced_fused_split(split_env, np, cnt, forced);
+    // The sixteen-row kernel takes half items: the schedule may cut the items of a last, mostly idle round in two.  A half costs
+    // about kFusedHalfCost of its item (64 of 128 rows with all the weights streamed: profiles/r04_mlp_halves.log), and the
+    // cost model is good to about 5 %: a split the model likes by at least 3 % is TIMED against the whole items on this very
+    // step's rows (three launches each, the first not counted; the launch is idempotent) and kept only if it is faster --
+    // once per set of tile counts (ANI_FUSED_AUTOTUNE=0: no timing, a split needs 8 % by the model).
+    const size_t cap = (size_t)2 * std::max(nitems, 1) + bins + 1;
+    std::vector<int> items((size_t)2 * std::max(nitems, 1)), off(bins + 1), split(np, 0);
+    int nsched = nitems;
+    const int split_mode = !gen ? 0 : (h->mlp_fused_halves == 2 ? 2 : (sub != 2 ? h->mlp_fused_halves : 0));   // searched for 128-row tiles only
+    (void)fused_schedule_halves(np, cnt, cost, half_cost, bins, split_mode, forced_split, split.data(), items.data(), off.data(), &nsched,
+                                autotune && split_mode == 1 ? 0.03 : 0.08);
+    int any_split = 0;
+    for (int q = 0; q < np; q++) any_split += split[q];
+    int rc = upload_fused_schedule(h, items, nsched, off, cap, st);
+    if (rc) return rc;
+    if (autotune && split_mode == 1 && any_split && !forced_split) {
+      float t_split = 0.f, t_whole = 0.f;
+      rc = time_fused_schedule(h, G, arith, bins, st, &t_split);
+      if (rc) return rc;
+      std::vector<int> items_w((size_t)std::max(nitems, 1)), off_w(bins + 1);
+      int n_w = nitems;
+      (void)fused_schedule_halves(np, cnt, cost, half_cost, bins, 0, nullptr, nullptr, items_w.data(), off_w.data(), &n_w);
+      rc = upload_fused_schedule(h, items_w, n_w, off_w, cap, st);
+      if (!rc) rc = time_fused_schedule(h, G, arith, bins, st, &t_whole);
+      if (!rc && t_split < t_whole) rc = upload_fused_schedule(h, items, nsched, off, cap, st);   // the split stays: back it goes
+      if (rc) return rc;
+      if (verbose)
+        fprintf(stderr, "libani_hip: fused MLP schedule, %d items: whole %.4f ms, with half items %.4f ms per launch -> %s\n", nitems,
+                t_whole / 2, t_split / 2, t_split < t_whole ? "halves" : "whole");
+    }
+    h->sched_key[0] = total; h->sched_key[1] = per_tile; h->sched_key[2] = mix; h->sched_key[3] = bins;
+  }
+  G.sched_items = h->fused_sched.p;
+  G.sched_off = h->fused_sched.p + h->sched_nitems;
+  G.sched_blocks = bins;
+  return ANI_OK;
+}
+
+// the launch, then the members' dE/dAEV copies -> the step's
+int launch_fused(ani_handle* h, const FusedArgs& G, MlpArith arith, int gen, int sub, hipStream_t st) {
   if (gen) {
     HIP_TRY(h, launch_mlp_fused16(G, arith, sub == 2 ? 4 : 8, st));
     h->last_mlp_kernel = arith == MLP_F16X2 ? (sub == 2 ? "mlp_fused16<2, 4>" : "mlp_fused16<2, 8>") : (sub == 2 ? "mlp_fused16<3, 4>" : "mlp_fused16<3, 8>");
@@ -917,11 +939,23 @@ int compute_mlp_fused(ani_handle* h, hipStream_t st) {
     HIP_TRY(h, launch_mlp_fused(G, arith, st));
     h->last_mlp_kernel = arith == MLP_F16X2 ? "mlp_fused<2>" : "mlp_fused<3>";
   }
-  if (G.member_items && h->dv_force)
-    launch_dev_parts(h->gaev_parts.p, G.part_stride, m.M, h->gaev.p, (long long)h->nrows * ka, /*sum=*/1, st);
-  else if (G.member_items)
-    launch_sum_parts(h->gaev_parts.p, G.part_stride, m.M, h->gaev.p, (long long)h->nrows * ka, st);
+  const long long n = (long long)h->nrows * h->ap_run.aev_stride;
+  if (G.member_items && h->dv_force) launch_dev_parts(h->gaev_parts.p, G.part_stride, G.M, h->gaev.p, n, /*sum=*/1, st);
+  else if (G.member_items) launch_sum_parts(h->gaev_parts.p, G.part_stride, G.M, h->gaev.p, n, st);
   return ANI_OK;
+}
+
+int compute_mlp_fused(ani_handle* h, hipStream_t st) {
+  const MlpArith arith = h->mlp_arith;
+  const int gen = h->mlp_fused_gen ? 1 : 0, fi = (arith == MLP_F16X2 ? 1 : 0) + 2 * gen;
+  int rc = ensure_fused(h, arith, gen, st);
+  if (rc) return rc;
+  const int sub = fused_sub_tiles(h);
+  FusedArgs G{};
+  rc = fill_fused_args(h, fi, sub, G);
+  if (!rc && h->mlp_fused_sched) rc = ensure_fused_schedule(h, G, arith, gen, sub, st);
+  if (!rc) rc = launch_fused(h, G, arith, gen, sub, st);
+  return rc;
 }
 
 // The MLP ensemble for every species bucket, one grouped launch per layer (all species and members together).
@@ -2478,7 +2512,10 @@ int ani_debug_fused_schedule_halves(int ntypes, const int* count, const double* 
     return ANI_ERR_ARG;
   for (int j = 0; j < ntypes; j++)
     if (count[j] < 0 || !(cost[j] > 0.0)) return ANI_ERR_ARG;
-  const double T = fused_schedule_halves(ntypes, count, cost, half_ratio, bins, split_mode, split_out, items_out, off_out, n_items_out);
+  int forced[kMaxProblems];
+  const double T = fused_schedule_halves(ntypes, count, cost, half_ratio, bins, split_mode,
+                                         forced_fused_split(getenv("ANI_FUSED_SPLIT"), ntypes, count, forced), split_out, items_out, off_out,
+                                         n_items_out);
   if (makespan_out) *makespan_out = T;
   return ANI_OK;
 }

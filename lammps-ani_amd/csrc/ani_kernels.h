@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "ani_fused_host.h"
 #include "ani_model.h"
 
 namespace ani {
@@ -22,6 +23,10 @@ enum Epilogue { EPI_PLAIN = 0, EPI_CELU = 1, EPI_LAST = 2, EPI_BWD = 3 };
 // clears it).  One collector per host thread: a handle is driven from one thread at a time (include/ani_hip.h).
 void note_launch_error(hipError_t e);
 hipError_t take_launch_error();
+// CU count of the current device, cached at first use (256 when the query fails; the failure goes to note_launch_error)
+int device_num_cus();
+// raises `kernel`'s dynamic-LDS limit to `bytes`, once per (device, kernel): a pair is remembered only after success
+hipError_t raise_dynamic_lds(const void* kernel, int bytes);
 
 // C[rows][N] = epi( A[rows][K] * Bt[N][K]^T ), fp32 MFMA.  Batched over blockIdx.y (ensemble members).
 struct GemmArgs {
@@ -85,11 +90,12 @@ hipError_t launch_mlp_chain(const GemmArgs* layers, const int* epi, int nlayers,
 void free_chain_plan(ChainPlan& p);
 int mlp_chain_slots();   // workgroups the chain kernel can keep resident (2 per CU)
 
-// ---- the whole MLP of a row tile in one workgroup (ani_kernels_mlpf.hip) ----------------------------------------------
+// ---- the whole MLP of a row tile in one workgroup (ani_kernels_mlpg.hip; the 32-row generation: ani_kernels_mlpf.hip) ----
 // Networks with three hidden layers whose widths fit one of the compiled shapes (fused_shape_for >= 0), AEV width a multiple
 // of 16, split arithmetic.  Per species bucket: the weight stream (1 KB pieces in consumption order, members back to back:
 // fused_pieces_per_member each) and the constants block (fused_consts_floats floats per member: b0 | b1 | b2 | w3 padded to
-// the shape's tiles, then {b3, 1/scale of the six products, 0}).
+// the shape's tiles, then {b3, 1/scale of the six products, 0}).  The shapes, these sizes and the static schedule of a launch
+// (fused_schedule, fused_schedule_halves) are plain C++ in ani_fused_host.h.
 constexpr int kMaxProblems = 16;   // species buckets per launch
 struct FusedProb {
   const float* aev;             // [rows][aev_stride] rows of the bucket
@@ -121,10 +127,6 @@ struct FusedArgs {
   int sched_blocks;                   // workgroups the schedule was made for (= the grid)
   int* err_flag;                      // device error word: bit 4 = the weight ring's schedule broke (cannot happen: tests/ring_sim.cpp)
 };
-int fused_shape_for(int d1, int d2, int d3);          // -1: no compiled shape holds these widths
-void fused_shape_tiles(int shape, int nt[3]);         // 32-feature tiles of the three hidden layers
-int fused_consts_floats(int shape);
-long long fused_pieces_per_member(int shape, int acols, int P);
 // one product's share of a stream: src[row][k] (ld) -> NT x KS blocks of P pieces at dst (see ani_kernels_mlpf.hip);
 // chunk: 0, -1 (tile-major: the hidden backward products) or 4 for the dE/dAEV product (the kernel walks four output tiles
 // at a time through all k-steps)
@@ -136,23 +138,12 @@ hipError_t launch_mlp_fused(const FusedArgs& G, MlpArith arith, hipStream_t st);
 // that would leave CUs idle).  Its weight stream has its own order (launch_build_stream16, fused16_pieces_per_member); the
 // constants block is the 32-row kernel's.  FusedProb::ks0 / nt0 are not used (derived from acols).
 hipError_t launch_mlp_fused16(const FusedArgs& G, MlpArith arith, int waves, hipStream_t st);
-long long fused16_pieces_per_member(int shape, int acols, int P);
 int fused16_b1_chunks(int nt0);                 // dE/dAEV chunks of nt0 16-column tiles ...
 int fused16_b1_chunk_tiles(int nt0, int ci);    // ... and the tiles of chunk ci (16, then 8, then the rest)
 // NT x KS blocks (16-row output tiles from tile nt_off on, 32-deep k-steps) of src[row][k]; order 0: k-step-major, 1: tile-major;
 // identity: k-slots in column order (the AEV operand of the first product) instead of the accumulator order
 void launch_build_stream16(const float* src, int ld, int rows_valid, int k_valid, int NT, int KS, int order, int nt_off, int identity,
                            int P, float scale, unsigned short* dst, hipStream_t st);
-int fused_num_cus();
-// Static schedule of a launch: `nitem_types` kinds of work items (type j: count[j] items of relative cost[j], items numbered
-// type after type), `bins` workgroups.  Multifit: the smallest makespan T for which first-fit-decreasing packs every item into
-// the bins.  items_out[sum count]: item numbers, workgroup after workgroup; off_out[bins + 1].  Returns the makespan.
-// (Drawing items from a counter, costliest first, is list scheduling: at 100 002 water atoms -- 521 + 261 tiles of cost 1 and
-// 0.67 on 256 CUs -- its last 14 tiles start when most CUs have finished, makespan 3.35; first-fit finds 3.0.)
-double fused_schedule(int nitem_types, const int* count, const double* cost, int bins, int* items_out, int* off_out);
-// the same with half items for the sixteen-row kernel (ids total + 2 i + h); see ani_kernels_mlpf.hip
-double fused_schedule_halves(int nitem_types, const int* count, const double* cost, double half_ratio, int bins, int split_mode,
-                             int* split_out, int* items_out, int* off_out, int* n_items_out, double min_gain = 0.08);
 // dst[i] = sum over m < M of parts[m * part_stride + i], i < n (n a multiple of 4, 16-byte aligned pointers)
 void launch_sum_parts(const float* parts, long long part_stride, int M, float* dst, long long n, hipStream_t st);
 // diagnostic builds (-DABLF_STAMPS) only: cycles per phase summed over tiles; returns 0 in the shipped build

@@ -29,7 +29,6 @@
 
 #include <map>
 #include <mutex>
-#include <set>
 #include <utility>
 
 #include "ani_kernels.h"
@@ -2163,14 +2162,6 @@ bool aev_fast_path(const AevParams& p, int max_numneigh) {
   return (size_t)fast_wave_floats(c, true) * 4 * kWavesB <= 160 * 1024 && (size_t)fast_wave_floats(c, false) * 4 * kWaves <= 160 * 1024;
 }
 
-static int num_cus() {
-  static const int n = [] {
-    int dev = 0, v = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
 static const char* waves_env() { return "ANI_AEV_WAVES_PER_CU"; }  // experiment knob: cap on resident waves per CU
 // persistent grid of the fast path: as many workgroups as fit on the chip by LDS (at most 8 per CU)
 template <typename K>
@@ -2197,23 +2188,14 @@ static int persistent_blocks(K kernel, int nrows, int waves_per_block, size_t ld
   if (forced > 0 && forced * waves_per_block / 2 >= 1) per_cu = std::min(per_cu, std::max(1, forced / waves_per_block));
   if (per_cu < 1) per_cu = 1;
   const int need = (nrows + waves_per_block - 1) / waves_per_block;
-  const int fit = num_cus() * per_cu;
+  const int fit = device_num_cus() * per_cu;
   return need < fit ? need : fit;
 }
 
 template <typename K, typename... Extra>
 static void launch_fast(K kernel, const AevParams& p, const AevArgs& a, int waves, size_t lds, int cap, int rowf, hipStream_t st,
                         Extra... extra) {
-  // raising the dynamic-LDS limit is per kernel: once per instantiation
-  static std::set<std::pair<int, const void*>> raised;   // per device: a process may drive several
-  static std::mutex mtx;
-  {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mtx);
-    if (raised.insert(std::make_pair(dev, (const void*)kernel)).second)
-      note_launch_error(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
+  note_launch_error(raise_dynamic_lds((const void*)kernel, 160 * 1024));
   hipLaunchKernelGGL(kernel, dim3(persistent_blocks(kernel, a.kcount, waves, lds)), dim3(64 * waves), lds, st, p, a, cap, rowf,
                      extra...);
 }

@@ -1,10 +1,36 @@
 // ani_kernels_misc.hip — the small kernels around the two hot passes: position packing, rebuild-time list
 // preparation (what src/ani_csrc/ani.cpp:213-229 and models/lammps_ani.py:156-166 do with torch ops every
 // rebuild / every step), and the final reductions / unit conversion (src/ani_csrc/ani.cpp:246-262).
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "ani_kernels.h"
 #include "ani_scan.h"
 
 namespace ani {
+
+int device_num_cus() {
+  static const int ncu = [] {
+    int dev = 0, v = 256;
+    if (hipGetDevice(&dev) == hipSuccess) note_launch_error(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+    return v > 0 ? v : 256;
+  }();
+  return ncu;
+}
+
+hipError_t raise_dynamic_lds(const void* kernel, int bytes) {
+  static std::set<std::pair<int, const void*>> raised;   // per device: a process may drive several
+  static std::mutex mtx;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mtx);
+  if (raised.count(std::make_pair(dev, kernel))) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) raised.insert(std::make_pair(dev, kernel));
+  return e;
+}
 
 // Midpoint of the bounding box of all atoms of the rank, once per list epoch.  The fp32 copies of the positions are
 // taken relative to it: a sub-domain that sits 150 A from the origin of the simulation box would otherwise carry four
@@ -443,8 +469,28 @@ void launch_atom_virial(const void* acc, bool fp64, int natoms, int ncomp, doubl
                        fold_next, fold_nlocal);
 }
 
+// ---- the members' dE/dAEV copies of a fused MLP launch with (tile, member) work items (FusedArgs::member_items) ------------------
+__global__ __launch_bounds__(256) void sum_parts_kernel(const float4* __restrict__ parts, long long stride4, int M, float4* __restrict__ dst,
+                                                        long long n4) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  float4 a = parts[i];
+  for (int m = 1; m < M; m++) {
+    const float4 b = parts[(long long)m * stride4 + i];
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+  }
+  dst[i] = a;
+}
+void launch_sum_parts(const float* parts, long long part_stride, int M, float* dst, long long n, hipStream_t st) {
+  const long long n4 = n / 4;
+  if (n4 <= 0) return;
+  hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(parts),
+                     part_stride / 4, M, reinterpret_cast<float4*>(dst), n4);
+}
+
+
 // ---- ensemble model deviation (ani_request_model_deviation): only on armed steps -----------------------------------------------
-// The armed replacement of sum_parts_kernel (ani_kernels_mlpf.hip): the mean in its order, then dg_m = M p_m - mean in place.
+// The armed replacement of sum_parts_kernel: the mean in its order, then dg_m = M p_m - mean in place.
 __global__ __launch_bounds__(256) void dev_parts_kernel(float4* __restrict__ parts, long long stride4, int M, float4* __restrict__ dst,
                                                         long long n4, int sum) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -805,14 +805,7 @@ __global__ __launch_bounds__(256, 3) void mlp_pipeline_x2(const GemmArgs* __rest
   }
 }
 
-int mlp_chain_slots() {
-  static const int n = [] {
-    int dev = 0, v = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return 2 * (v > 0 ? v : 256);
-  }();
-  return n;
-}
+int mlp_chain_slots() { return 2 * device_num_cus(); }
 
 void free_chain_plan(ChainPlan& p) {
   if (p.d_done) (void)hipFree(p.d_done);
@@ -972,11 +965,7 @@ static double makespan(const GemmArgs* probs, int nprob, int R, int ncu) {
 void launch_gemm_group(const GemmArgs* probs, int nprob, Epilogue epi, hipStream_t st, MlpArith arith) {
   const bool split_bf16 = arith != MLP_FP32;
   static const int forced = [] { const char* e = getenv("ANI_GEMM_WM"); return e ? atoi(e) : 0; }();
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = device_num_cus();
   for (int base = 0; base < nprob; base += kMaxProblems) {
     const int np = nprob - base < kMaxProblems ? nprob - base : kMaxProblems;
     int WM = forced;

@@ -34,14 +34,7 @@
 // forward pass; the backward products write each gradient over the activation it is masked with, their source held as
 // 16-bit fragments (g3: 120, g2: 144), so 128 + 96 + 120 + an accumulator while g2 is formed.  One workgroup per CU; tiles
 // are handed out from a counter, costliest species first.
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <set>
-#include <utility>
-#include <vector>
 
 #include "ani_fused_ring.h"
 #include "ani_kernels.h"
@@ -688,6 +681,10 @@ __device__ __forceinline__ void fused_tile(const TileCtx& cx, const FusedProb& p
 }
 #undef RING_T
 
+// the tiles of compiled shape s (ani_fused_host.h), as template arguments
+#define SHAPE_T(s) kFusedShapes[s][0], kFusedShapes[s][1], kFusedShapes[s][2]
+static_assert(kNumFusedShapes == 3, "mlp_fused has one case per compiled shape");
+
 template <int P>
 __global__ __launch_bounds__(256, 1) void mlp_fused(FusedArgs G) {
   extern __shared__ uint4 smem4[];
@@ -724,31 +721,13 @@ __global__ __launch_bounds__(256, 1) void mlp_fused(FusedArgs G) {
     const FusedProb& pr = G.p[pi];
     const int tile = t - G.tile_start[pi];
     switch (pr.shape) {
-      case 0: fused_tile<8, 6, 5, P>(cx, pr, tile, wave, lane, ring, cst); break;
-      case 1: fused_tile<6, 5, 4, P>(cx, pr, tile, wave, lane, ring, cst); break;
-      default: fused_tile<5, 4, 3, P>(cx, pr, tile, wave, lane, ring, cst); break;
+      case 0: fused_tile<SHAPE_T(0), P>(cx, pr, tile, wave, lane, ring, cst); break;
+      case 1: fused_tile<SHAPE_T(1), P>(cx, pr, tile, wave, lane, ring, cst); break;
+      default: fused_tile<SHAPE_T(2), P>(cx, pr, tile, wave, lane, ring, cst); break;
     }
   }
 }
-
-const int kShapes[3][3] = {{8, 6, 5}, {6, 5, 4}, {5, 4, 3}};
-
-int fused_shape_for(int d1, int d2, int d3) {
-  for (int s = 2; s >= 0; s--)
-    if (d1 <= 32 * kShapes[s][0] && d2 <= 32 * kShapes[s][1] && d3 <= 32 * kShapes[s][2]) return s;
-  return -1;
-}
-void fused_shape_tiles(int shape, int nt[3]) { for (int k = 0; k < 3; k++) nt[k] = kShapes[shape][k]; }
-int fused_consts_floats(int shape) {
-  const int* s = kShapes[shape];
-  const int n = 32 * (s[0] + s[1] + 2 * s[2]) + 8;
-  return (n + 255) / 256 * 256;   // whole 1 KB pieces
-}
-long long fused_pieces_per_member(int shape, int acols, int P) {
-  const int* s = kShapes[shape];
-  const long long ks0 = acols / 16, nt0 = (acols + 31) / 32;
-  return P * (ks0 * s[0] + 2LL * s[0] * s[1] + 2LL * s[1] * s[2] + 2LL * s[2] * s[1] + 2LL * s[1] * s[0] + 2LL * s[0] * nt0);
-}
+#undef SHAPE_T
 
 int fused_read_stamps(unsigned long long* out16, int reset) {
 #ifdef ABLF_STAMPS
@@ -764,24 +743,6 @@ int fused_read_stamps(unsigned long long* out16, int reset) {
 #endif
 }
 
-__global__ __launch_bounds__(256) void sum_parts_kernel(const float4* __restrict__ parts, long long stride4, int M, float4* __restrict__ dst,
-                                                        long long n4) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  float4 a = parts[i];
-  for (int m = 1; m < M; m++) {
-    const float4 b = parts[(long long)m * stride4 + i];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-  }
-  dst[i] = a;
-}
-void launch_sum_parts(const float* parts, long long part_stride, int M, float* dst, long long n, hipStream_t st) {
-  const long long n4 = n / 4;
-  if (n4 <= 0) return;
-  hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(parts),
-                     part_stride / 4, M, reinterpret_cast<float4*>(dst), n4);
-}
-
 void launch_build_stream(const float* src, int ld, int rows_valid, int k_valid, int NT, int KS, int chunk, int P, float scale,
                          unsigned short* dst, hipStream_t st) {
   const long long total = (long long)NT * KS * 512;
@@ -790,151 +751,8 @@ void launch_build_stream(const float* src, int ld, int rows_valid, int k_valid, 
                      chunk, P, scale, dst);
 }
 
-int fused_num_cus() {
-  static int ncu = [] {
-    int dev = 0, v = 256;
-    if (hipGetDevice(&dev) == hipSuccess) note_launch_error(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    return v > 0 ? v : 256;
-  }();
-  return ncu;
-}
-
-namespace {
-// multifit: the smallest makespan T for which first-fit-decreasing packs every item; take[b * ntypes + j] = items of type j in bin b
-double fused_pack(int ntypes, const int* count, const double* cost, int bins, std::vector<int>& best) {
-  std::vector<int> order(ntypes);
-  for (int j = 0; j < ntypes; j++) order[j] = j;
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-  double total = 0.0, cmax = 0.0;
-  for (int j = 0; j < ntypes; j++) { total += count[j] * cost[j]; if (count[j] > 0) cmax = std::max(cmax, cost[j]); }
-  std::vector<int> take((size_t)bins * ntypes);
-  auto fits = [&](double T) {
-    std::fill(take.begin(), take.end(), 0);
-    std::vector<double> rem(bins, T);
-    for (int jj = 0; jj < ntypes; jj++) {
-      const int j = order[jj];
-      int left = count[j];
-      if (left == 0 || cost[j] <= 0.0) { if (left) { take[j] += left; } continue; }
-      for (int b = 0; b < bins && left > 0; b++) {
-        const int k = std::min(left, (int)((rem[b] + 1e-9) / cost[j]));
-        if (k > 0) { take[(size_t)b * ntypes + j] = k; rem[b] -= k * cost[j]; left -= k; }
-      }
-      if (left > 0) return false;
-    }
-    return true;
-  };
-  double lo = std::max(total / bins, cmax), hi = lo;
-  while (!fits(hi)) hi *= 1.25;
-  best = take;
-  for (int it = 0; it < 24 && hi - lo > 1e-3 * hi; it++) {
-    const double mid = 0.5 * (lo + hi);
-    if (fits(mid)) { hi = mid; best = take; } else lo = mid;
-  }
-  return hi;
-}
-}  // namespace
-
-double fused_schedule(int ntypes, const int* count, const double* cost, int bins, int* items_out, int* off_out) {
-  std::vector<int> best, first(ntypes + 1, 0), order(ntypes);
-  for (int j = 0; j < ntypes; j++) { order[j] = j; first[j + 1] = first[j] + count[j]; }
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-  const double T = fused_pack(ntypes, count, cost, bins, best);
-  std::vector<int> next(first.begin(), first.end() - 1);
-  int n = 0;
-  for (int b = 0; b < bins; b++) {
-    off_out[b] = n;
-    for (int jj = 0; jj < ntypes; jj++) {
-      const int j = order[jj];
-      for (int k = 0; k < best[(size_t)b * ntypes + j]; k++) items_out[n++] = next[j]++;
-    }
-  }
-  off_out[bins] = n;
-  return T;
-}
-
-// The same with HALF items (the sixteen-row kernel: item total + 2 i + h = half h of item i, run by the lower half of a
-// workgroup's waves at half_ratio of the item's cost -- more than half: the weights stream through the workgroup all the same).
-// The last split[j] items of type j are cut in two where that shortens the schedule: the items beyond the last full round of
-// workgroups otherwise make a round of their own with most of the chip idle.  split_mode 1: searched (a few candidate counts per
-// type, most expensive types first, two sweeps; kept only if the makespan falls by min_gain -- the cost model is good to about
-// 5 %: the caller either asks for 8 % or times the candidate against the whole items), 2: every item (tests, measurements).
-// items_out holds up to sum(count) + max splits entries.  Returns the makespan; *n_items_out = entries written.
-double fused_schedule_halves(int ntypes, const int* count, const double* cost, double half_ratio, int bins, int split_mode, int* split_out,
-                             int* items_out, int* off_out, int* n_items_out, double min_gain) {
-  std::vector<int> first(ntypes + 1, 0);
-  for (int j = 0; j < ntypes; j++) first[j + 1] = first[j] + count[j];
-  const int total = first[ntypes];
-  std::vector<int> split(ntypes, 0), ecount(2 * ntypes), best;
-  std::vector<double> ecost(2 * ntypes);
-  for (int j = 0; j < ntypes; j++) { ecost[j] = cost[j]; ecost[ntypes + j] = half_ratio * cost[j]; }
-  auto makespan = [&](const std::vector<int>& sp, std::vector<int>& take) {
-    for (int j = 0; j < ntypes; j++) { ecount[j] = count[j] - sp[j]; ecount[ntypes + j] = 2 * sp[j]; }
-    return fused_pack(2 * ntypes, ecount.data(), ecost.data(), bins, take);
-  };
-  double T = makespan(split, best);
-  if (const char* e = getenv("ANI_FUSED_SPLIT")) {   // experiments: "k0,k1,..." = how many of each type's last items to cut
-    int j = 0;
-    for (const char* q = e; *q && j < ntypes; j++) {
-      split[j] = std::max(0, std::min(count[j], atoi(q)));
-      while (*q && *q != ',') q++;
-      if (*q == ',') q++;
-    }
-    T = makespan(split, best);
-  } else if (split_mode == 2) {
-    for (int j = 0; j < ntypes; j++) split[j] = count[j];
-    T = makespan(split, best);
-  } else if (split_mode == 1) {
-    const double T0 = T;
-    std::vector<int> order(ntypes), cur = split, take;
-    for (int j = 0; j < ntypes; j++) order[j] = j;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] * count[a] > cost[b] * count[b]; });
-    double Tc = T;
-    for (int sweep = 0; sweep < 2; sweep++)
-      for (int jj = 0; jj < ntypes && jj < 4; jj++) {
-        const int j = order[jj];
-        if (count[j] == 0) continue;
-        const int cap = std::min(count[j], bins);
-        const int cand[7] = {0, count[j] % bins, cap / 8, cap / 4, cap / 2, (3 * cap) / 4, cap};
-        int keep = cur[j];
-        for (int c : cand) {
-          if (c < 0 || c > count[j]) continue;
-          std::vector<int> trial = cur;
-          trial[j] = c;
-          const double Tt = makespan(trial, take);
-          if (Tt < Tc * (1.0 - 1e-6)) { Tc = Tt; keep = c; }
-        }
-        cur[j] = keep;
-      }
-    if (Tc < (1.0 - min_gain) * T0) { split = cur; T = makespan(split, best); }
-    else T = makespan(split, best);
-  }
-  // numbering: type j's whole items first[j] .. first[j] + count[j] - split[j]; the halves of the split[j] items behind them
-  std::vector<int> order(2 * ntypes), next(2 * ntypes, 0);
-  for (int j = 0; j < 2 * ntypes; j++) order[j] = j;
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return ecost[a] > ecost[b]; });
-  int n = 0;
-  for (int b = 0; b < bins; b++) {
-    off_out[b] = n;
-    for (int jj = 0; jj < 2 * ntypes; jj++) {
-      const int e = order[jj];
-      for (int k = 0; k < best[(size_t)b * 2 * ntypes + e]; k++) {
-        const int i = next[e]++;
-        if (e < ntypes) items_out[n++] = first[e] + i;
-        else {
-          const int j = e - ntypes;
-          items_out[n++] = total + 2 * (first[j] + count[j] - split[j] + (i >> 1)) + (i & 1);
-        }
-      }
-    }
-  }
-  off_out[bins] = n;
-  if (split_out) for (int j = 0; j < ntypes; j++) split_out[j] = split[j];
-  if (n_items_out) *n_items_out = n;
-  return T;
-}
-
 hipError_t launch_mlp_fused(const FusedArgs& G, MlpArith arith, hipStream_t st) {
-  const int ncu = fused_num_cus();
+  const int ncu = device_num_cus();
   const int total = G.tile_start[G.nprob] * (G.member_items ? G.M : 1);
   if (total <= 0) return hipSuccess;
   hipError_t e = hipSuccess;
@@ -942,20 +760,8 @@ hipError_t launch_mlp_fused(const FusedArgs& G, MlpArith arith, hipStream_t st) 
   if (e != hipSuccess) return e;
   const int pi = arith == MLP_F16X2 ? 1 : 0;
   const void* fn = pi ? (const void*)mlp_fused<2> : (const void*)mlp_fused<3>;
-  {
-    // raising the dynamic-LDS limit is per kernel and device: once each
-    static std::set<std::pair<int, const void*>> raised;
-    static std::mutex mtx;
-    int dev = 0;
-    e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mtx);
-    if (!raised.count(std::make_pair(dev, fn))) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLds);
-      if (e != hipSuccess) return e;
-      raised.insert(std::make_pair(dev, fn));
-    }
-  }
+  e = raise_dynamic_lds(fn, kFusedLds);
+  if (e != hipSuccess) return e;
   const int grid = G.sched_items ? G.sched_blocks : (total < ncu ? total : ncu);
   if (pi) hipLaunchKernelGGL(mlp_fused<2>, dim3(grid), dim3(256), kFusedLds, st, G);
   else hipLaunchKernelGGL(mlp_fused<3>, dim3(grid), dim3(256), kFusedLds, st, G);

@@ -27,9 +27,6 @@
 // front of the LAST block of slab j - 1 and starts the loads of slab j + 1 (one piece per block and wave).
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <set>
-#include <utility>
 
 #include "ani_kernels.h"
 #include "ani_mlp_common.h"
@@ -601,6 +598,10 @@ __device__ __forceinline__ void g_tile(const GTileCtx& cx, const FusedProb& pr, 
   }
 }
 
+// the 16-feature tiles of compiled shape s (ani_fused_host.h: twice its 32-feature tiles), as template arguments
+#define SHAPE16_T(s) 2 * kFusedShapes[s][0], 2 * kFusedShapes[s][1], 2 * kFusedShapes[s][2]
+static_assert(kNumFusedShapes == 3, "mlp_fused16 has one case per compiled shape");
+
 template <int P, int W>
 __global__ __launch_bounds__(64 * W, 1) void mlp_fused16(FusedArgs G) {
   extern __shared__ uint4 smem4g[];
@@ -649,32 +650,26 @@ __global__ __launch_bounds__(64 * W, 1) void mlp_fused16(FusedArgs G) {
     const bool act = hf < 0 || wave < W / 2;
     if (act) {
       switch (pr.shape) {
-        case 0: g_tile<16, 12, 10, P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
-        case 1: g_tile<12, 10, 8, P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
-        default: g_tile<10, 8, 6, P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
+        case 0: g_tile<SHAPE16_T(0), P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
+        case 1: g_tile<SHAPE16_T(1), P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
+        default: g_tile<SHAPE16_T(2), P, W, true>(cx, pr, row0, wave, lane, ring, cst); break;
       }
     } else {
       switch (pr.shape) {
-        case 0: g_tile<16, 12, 10, P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
-        case 1: g_tile<12, 10, 8, P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
-        default: g_tile<10, 8, 6, P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
+        case 0: g_tile<SHAPE16_T(0), P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
+        case 1: g_tile<SHAPE16_T(1), P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
+        default: g_tile<SHAPE16_T(2), P, W, false>(cx, pr, row0, wave, lane, ring, cst); break;
       }
     }
   }
 }
+#undef SHAPE16_T
 
-long long fused16_pieces_per_member(int shape, int acols, int P) {
-  int nt[3];
-  fused_shape_tiles(shape, nt);   // 32-feature tiles
-  const long long n1 = 2 * nt[0], n2 = 2 * nt[1], n3 = 2 * nt[2];
-  const long long ks1 = (acols + 31) / 32, nt0 = (acols + 15) / 16;
-  return P * (ks1 * n1 + (n1 / 2) * n2 + (n2 / 2) * n3 + n2 * (n3 / 2) + n1 * (n2 / 2) + nt0 * (n1 / 2));
-}
 int fused16_b1_chunks(int nt0) { return g_b1_chunks(nt0); }
 int fused16_b1_chunk_tiles(int nt0, int ci) { return g_b1_chunk_tiles(nt0, ci); }
 
 hipError_t launch_mlp_fused16(const FusedArgs& G, MlpArith arith, int waves, hipStream_t st) {
-  const int ncu = fused_num_cus();
+  const int ncu = device_num_cus();
   const int total = G.tile_start[G.nprob] * (G.member_items ? G.M : 1);
   if (total <= 0) return hipSuccess;
   hipError_t e = hipSuccess;
@@ -683,19 +678,8 @@ hipError_t launch_mlp_fused16(const FusedArgs& G, MlpArith arith, int waves, hip
   const bool f16 = arith == MLP_F16X2;
   const void* fn = waves == 8 ? (f16 ? (const void*)mlp_fused16<2, 8> : (const void*)mlp_fused16<3, 8>)
                               : (f16 ? (const void*)mlp_fused16<2, 4> : (const void*)mlp_fused16<3, 4>);
-  {
-    static std::set<std::pair<int, const void*>> raised;
-    static std::mutex mtx;
-    int dev = 0;
-    e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mtx);
-    if (!raised.count(std::make_pair(dev, fn))) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kGLds);
-      if (e != hipSuccess) return e;
-      raised.insert(std::make_pair(dev, fn));
-    }
-  }
+  e = raise_dynamic_lds(fn, kGLds);
+  if (e != hipSuccess) return e;
   const int grid = G.sched_items ? G.sched_blocks : (total < ncu ? total : ncu);
   if (waves == 8) {
     if (f16) hipLaunchKernelGGL((mlp_fused16<2, 8>), dim3(grid), dim3(512), kGLds, st, G);

@@ -1,5 +1,6 @@
 // ring_sim.cpp — CPU replay of the weight slots of the fused MLP kernel (lammps-ani_amd/csrc/ani_fused_ring.h: the very
-// functions the kernel runs) for every compiled shape, both arithmetics, every AEV width and member count of interest.
+// functions the kernel runs) for every compiled shape (the table and the stream's size: ani_fused_host.h, the very ones the
+// host runs), both arithmetics, every AEV width and member count of interest.
 // Mirrors the order of the boundaries in ani_kernels_mlpf.hip:fused_tile (slab 0 issued at the start of a tile; at boundary j
 // the wait, the barrier, then the loads of slab j + 1) and checks, at every boundary, that
 //   (1) the slab about to be read was issued, with the size the consumer expects, into the slot the consumer reads,
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "ani_fused_host.h"
 #include "ani_fused_ring.h"
 
 using namespace ani;
@@ -56,12 +58,12 @@ struct Sim {
     consumed++;
     issue_next<NT1, NT2, NT3, P>();
   }
-  template <int NT1, int NT2, int NT3, int P>
+  template <int S, int P>
   void tile(int ks0, int nt0, int M) {
+    constexpr int NT1 = kFusedShapes[S][0], NT2 = kFusedShapes[S][1], NT3 = kFusedShapes[S][2];
     constexpr int K1 = F1Slab<NT1, P>::k;
     for (int& s : slot_slab) s = -1;
-    // pieces per member (ani_kernels_mlpf.hip:fused_pieces_per_member)
-    const long long ppm = (long long)P * ((long long)ks0 * NT1 + 2LL * NT1 * NT2 + 2LL * NT2 * NT3 + 2LL * NT3 * NT2 + 2LL * NT2 * NT1 + 2LL * NT1 * nt0);
+    const long long ppm = fused_pieces_per_member(S, 16 * ks0, P);   // an AEV of ks0 k-steps: nt0 = (ks0 + 1) / 2 tiles
     ring_reset<NT1, NT2, NT3, P>(r, nullptr, (int)(ppm * M), ks0, nt0);
     issue_next<NT1, NT2, NT3, P>();
     for (int m = 0; m < M && ok; m++) {
@@ -89,14 +91,15 @@ struct Sim {
   }
 };
 
-template <int NT1, int NT2, int NT3, int P>
+template <int S, int P>   // compiled shape S of the table
 static long long sweep(int& bad) {
+  constexpr int NT1 = kFusedShapes[S][0], NT2 = kFusedShapes[S][1], NT3 = kFusedShapes[S][2];
   long long checks = 0;
   for (int ks0 = 1; ks0 <= 64; ks0++)
     for (int M = 1; M <= 3; M++) {
       const int nt0 = (ks0 + 1) / 2;   // both follow from the AEV width
       Sim s;
-      s.tile<NT1, NT2, NT3, P>(ks0, nt0, M);
+      s.tile<S, P>(ks0, nt0, M);
       checks += s.checks;
       if (!s.ok) {
         std::printf("FAIL shape (%d,%d,%d) P=%d ks0=%d nt0=%d M=%d: %s\n", NT1, NT2, NT3, P, ks0, nt0, M, s.what);
@@ -110,8 +113,9 @@ static long long sweep(int& bad) {
 int main() {
   int bad = 0;
   long long checks = 0;
-  checks += sweep<8, 6, 5, 3>(bad); checks += sweep<6, 5, 4, 3>(bad); checks += sweep<5, 4, 3, 3>(bad);
-  checks += sweep<8, 6, 5, 2>(bad); checks += sweep<6, 5, 4, 2>(bad); checks += sweep<5, 4, 3, 2>(bad);
+  static_assert(kNumFusedShapes == 3, "one sweep per compiled shape and arithmetic");
+  checks += sweep<0, 3>(bad); checks += sweep<1, 3>(bad); checks += sweep<2, 3>(bad);
+  checks += sweep<0, 2>(bad); checks += sweep<1, 2>(bad); checks += sweep<2, 2>(bad);
   std::printf("ring_sim: %lld boundaries replayed, %d failing configurations\n", checks, bad);
   return bad ? 1 : 0;
 }

@@ -1,7 +1,7 @@
 """CPU: the weight slots of the fused MLP kernel, replayed on the host.
 
 tests/ring_sim.cpp includes lammps-ani_amd/csrc/ani_fused_ring.h -- the very bookkeeping functions the HIP kernel runs --
-and walks the kernel's boundary sequence for every compiled shape, both arithmetics, AEV widths from 16 to 1024 columns
+and ani_fused_host.h -- the host's table of compiled shapes and its formula for the stream's size -- and walks the kernel's boundary sequence for every compiled shape, both arithmetics, AEV widths from 16 to 1024 columns
 and one to three ensemble members: every boundary must find the slab it expects (size and slot) already issued, and no
 load may write a slot whose slab a wave may still be reading (a boundary can stand in front of the last block of the slab
 before)."""

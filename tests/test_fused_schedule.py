@@ -1,4 +1,4 @@
-"""CPU: the static schedule of the fused MLP launch (ani_kernels_mlpf.hip:fused_schedule, through ani_debug_fused_schedule).
+"""CPU: the static schedule of the fused MLP launch (ani_fused_host.h:fused_schedule, through ani_debug_fused_schedule).
 
 Which workgroup runs which tiles is decided on the host by multifit (the smallest makespan for which first-fit-decreasing
 packs the tiles into the CUs).  Properties: every item exactly once; a workgroup's list in descending cost; makespan never
@@ -37,9 +37,14 @@ def _list_scheduling(count, cost, bins):
     return max(loads)
 
 
+# one workgroup with an empty type; fewer items than workgroups; one costly item past a full round; exactly one round; kMaxProblems types
+EDGE_ROWS = [([7, 0, 3], [2.0, 9.0, 2.0], 1), ([5, 5], [3.0, 3.0], 256), ([257, 1], [440.0, 296.0], 256), ([256, 0], [440.0, 296.0], 256),
+             ([3] * 16, [float(c) for c in range(16, 0, -1)], 5)]
+
+
 @pytest.mark.parametrize("count,cost,bins", [([521, 261], [440.0, 296.0], 256), ([66, 33], [440.0, 296.0], 256), ([1], [5.0], 8),
                                              ([424, 216], [440.0, 296.0], 256), ([300, 200, 100, 7], [284.0, 284.0, 284.0, 91.0], 256),
-                                             ([5000, 3000], [440.0, 296.0], 256), ([3, 2, 9], [1.0, 7.5, 2.25], 4)])
+                                             ([5000, 3000], [440.0, 296.0], 256), ([3, 2, 9], [1.0, 7.5, 2.25], 4)] + EDGE_ROWS)
 def test_schedule_is_a_partition_and_beats_the_counter(count, cost, bins):
     items, off, mk = _schedule(count, cost, bins)
     n = int(np.sum(count))
@@ -84,7 +89,7 @@ def _schedule_halves(count, cost, bins, mode, ratio=0.75):
 
 @pytest.mark.parametrize("count,cost,bins", [([521, 261], [440.0, 296.0], 256), ([261, 131], [440.0, 296.0], 256), ([66, 33], [440.0, 296.0], 256),
                                              ([424, 216], [440.0, 296.0], 256), ([1], [5.0], 8), ([300, 200, 100, 7], [284.0, 284.0, 284.0, 91.0], 256),
-                                             ([5000, 3000], [440.0, 296.0], 256), ([3, 2, 9], [1.0, 7.5, 2.25], 4)])
+                                             ([5000, 3000], [440.0, 296.0], 256), ([3, 2, 9], [1.0, 7.5, 2.25], 4)] + EDGE_ROWS)
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_schedule_with_half_items_covers_every_item_once(count, cost, bins, mode):
     """Every item runs exactly once: whole, or as its two halves (ids n + 2 i + h); the halves are the LAST split[j] items of a type;

@@ -288,3 +288,39 @@ def test_mlp_fused_1_and_2_agree_bit_for_bit_with_eight_members(arith, gen, mode
     b = _rows_and_eatom(path, inp, dict(mlp_fused=2, mlp_fused_gen=gen), arith)
     assert a[2] == b[2]
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("arith", [1, 2], ids=["arith1-bf16x3", "arith2-f16x2"])
+def test_one_handle_across_list_epochs_agrees_bit_for_bit_with_fresh_handles(arith, model_cache):
+    """One handle through five list epochs (ago = 0) that change the tile counts, the species present (the weight streams are
+    re-made for the pruned AEV layout) and the schedule's options: what it keeps between epochs -- the static schedule and its
+    key, the streams -- must give the bits of a fresh handle with the same options on the same box, real rows of dE/dAEV and
+    every atom's energy.  Per-species counts on different tile edges in both boxes; mlp_fused_halves 0 or 2 only, so no timed
+    decision enters."""
+    path = model_cache("ani2x", 2, 41)
+    X = hx.decompose(_system([129, 15, 1, 64, 33, 127, 17]))     # 386 atoms
+    Y = hx.decompose(_system([257, 31, 0, 128, 65, 16, 63]))     # 560 atoms, one species absent
+    P = 3 if arith == 1 else 2
+    opts = dict(mlp_fused=2, mlp_fused_rows=128, mlp_fused_halves=0, **G)
+    steps = [(X, {}, 8), (Y, {}, 8), (X, {}, 8), (X, dict(mlp_fused_halves=2), 8), (Y, dict(mlp_fused_rows=64), 4)]
+    ani = ani_hip.ANI(path, 0)
+    ani.set_option("mlp_arith", arith)
+    for k, v in opts.items():
+        ani.set_option(k, v)
+    for i, (inp, change, waves) in enumerate(steps):
+        opts.update(change)
+        for k, v in change.items():
+            ani.set_option(k, v)
+        g, e, _, rows = _gaev_eatom(ani, inp, 0)
+        assert ani.last_mlp_kernel() == "mlp_fused16<%d, %d>" % (P, waves), (i + 1, ani.last_mlp_kernel())
+        fresh = ani_hip.ANI(path, 0)
+        fresh.set_option("mlp_arith", arith)
+        for k, v in opts.items():
+            fresh.set_option(k, v)
+        g0, e0, _, rows0 = _gaev_eatom(fresh, inp, 0)
+        assert fresh.last_mlp_kernel() == ani.last_mlp_kernel()
+        fresh.close()
+        assert np.array_equal(rows, rows0)
+        assert np.array_equal(g[rows], g0[rows0]), f"step {i + 1}: dE/dAEV rows differ from a fresh handle's"
+        assert np.array_equal(e, e0), f"step {i + 1}: energies differ from a fresh handle's"
+    ani.close()
