@@ -256,6 +256,53 @@ int ani_build_list(ani_handle* h, int ntotal, int nlocal, const int64_t* species
 int ani_debug_list(ani_handle* h, const int** d_numneigh, const int** d_nbr_off, const int** d_jlist);
 
 /*
+ * Molecule finder: which molecules are in the box, from the list the step already keeps (the reference answers this outside the
+ * pair style, in a second GPU program over a dumped trajectory: examples/combustion/analyze.py -- a 2 A neighbour list, bonds by a
+ * per-element-pair length, connected components, a count per sorted formula).  Works on the list installed in the handle for this
+ * epoch (an ago == 0 call or ani_build_list*; dense segments or capacity rows).  Arms nothing, does not touch the step's state, may
+ * be called between any two steps.
+ *
+ * ani_set_bond_table   cut[nspecies][nspecies]: host doubles in Angstrom indexed by the model's species (ani_species_symbol names
+ *     them); symmetric; an entry <= 0 means "never bonded".  ANI_ERR_ARG when nspecies != ani_num_species(h), when the table is
+ *     asymmetric, or when an entry is above the smaller of the two AEV cutoffs (the list is only guaranteed complete inside the
+ *     force cutoff).  Copied to the device and kept until replaced; cut == NULL clears it.  There is no default table: the numbers
+ *     are the caller's chemistry.
+ * ani_find_molecules_device   every pointer is device memory on the handle's device, nothing synchronises, stream == NULL is the
+ *     HIP default stream.  ANI_ERR_ARG when no list is installed, no bond table is set, ntotal / nlocal differ from the epoch's,
+ *     or the handle is a half-list handle (use_fullnbr == 0).  Any output pointer may be NULL.
+ * ani_find_molecules   the same with host pointers: uploads the positions (and owner), runs the device entry on the handle's
+ *     stream, downloads and synchronises.
+ *
+ * Definitions.
+ *   Bond      a list entry (centre i, neighbour j) with |x_j - x_i|^2 <= cut[s_i][s_j]^2, evaluated in fp64 from the doubles passed
+ *             in: d_x / coordinates [ntotal*3], NOT the handle's packed fp32 positions.  The handle's precision does not matter.
+ *   Owner     a ghost neighbour g >= nlocal stands for the owned atom owner[g - nlocal] (int64 [ntotal - nlocal]).  owner == NULL
+ *             uses the maps of an installed ghost fold (ani_set_ghost_fold / staged) if there is one; otherwise every ghost counts
+ *             as foreign.  An owner value < 0 or >= nlocal marks a foreign ghost: an atom of another rank.
+ *   Molecule  a connected component of the owned atoms under bonds, ghosts replaced by their owners.  mol_of_atom[i] (int
+ *             [nlocal]) is the SMALLEST owned index in i's component: the labelling is canonical, independent of scheduling.
+ *   Open molecule   one with at least one bond to a foreign ghost.  Labelled like any other and counted in the summary, but left
+ *             out of the formula table: a one-rank call cannot know its composition.
+ *   Formula table   formula[formula_cap][S + 1] ints, S = ani_num_species(h): the count of each species, then the number of closed
+ *             molecules with that composition.  The host entry sorts the rows ascending, lexicographically by composition; the
+ *             device entry writes them in unspecified order.  More distinct compositions than formula_cap: the extra rows are
+ *             dropped (nothing is written past formula_cap rows), summary[1] still holds the number needed, and the host entry
+ *             returns ANI_ERR_CAPACITY.  Rows beyond summary[1] are not written.
+ *   Summary   summary[6] (int64): molecules; distinct closed compositions; open molecules; list entries accepted as bonds
+ *             (directed: a bond between two centres is met from both ends); atoms in the largest molecule; owned atoms in open
+ *             molecules.
+ * Six small launches (lammps-ani_amd/csrc/ani_kernels_mol.hip): a lock-free union-find over the list, a flattening pass, a tally
+ * of compositions in a hash table.  No kernel waits for another lane, wave or workgroup.
+ */
+int ani_set_bond_table(ani_handle* h, const double* cut, int nspecies);
+int ani_find_molecules_device(ani_handle* h, int ntotal, int nlocal, const double* d_x, const int64_t* d_owner, int* d_mol_of_atom,
+                              int* d_formula, int formula_cap, int64_t* d_summary, void* stream);
+int ani_find_molecules(ani_handle* h, int ntotal, int nlocal, const double* coordinates, const int64_t* owner, int* mol_of_atom,
+                       int* formula, int formula_cap, int64_t* summary);
+/* the model file's symbol of species s ("H", "C", ...; "" outside [0, ani_num_species)): valid until ani_destroy */
+const char* ani_species_symbol(const ani_handle* h, int s);
+
+/*
  * Ghost forces over RCCL instead of the caller's host MPI (the reference: comm->reverse_comm(this) after the D2H copy,
  * src/pair_ani.cpp:197-201,461-484).  With a communicator of include/ani_comm.h attached (maps of the epoch installed by the
  * caller: ani_comm_set_epoch, and ani_comm_set_ghost_order when the ghost block is in LAMMPS' swap order), the host-pointer

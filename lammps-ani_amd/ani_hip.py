@@ -23,7 +23,8 @@ EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani
            "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_set_option", "ani_phase_timing", "ani_phase_times",
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
            "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
-           "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts"]
+           "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts",
+           "ani_set_bond_table", "ani_find_molecules_device", "ani_find_molecules", "ani_species_symbol"]
 # include/ani_comm.h: the device-side ghost exchange over RCCL
 COMM_EXPORTS = ["ani_comm_get_unique_id", "ani_comm_create", "ani_comm_create_local", "ani_comm_destroy", "ani_comm_last_error", "ani_comm_rank",
                 "ani_comm_size", "ani_comm_plan", "ani_comm_exchange_counts", "ani_comm_alltoallv", "ani_comm_set_epoch",
@@ -101,6 +102,13 @@ def lib():
         L.ani_request_atom_virial.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ani_request_model_deviation.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ani_debug_deviation_parts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.ani_set_bond_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ani_find_molecules_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p]
+        L.ani_find_molecules.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p]
+        L.ani_species_symbol.argtypes = [C.c_void_p, C.c_int]
+        L.ani_species_symbol.restype = C.c_char_p
         L.ani_host_register.argtypes = [C.c_void_p, C.c_size_t]
         L.ani_host_unregister.argtypes = [C.c_void_p]
         L.ani_last_mlp_kernel.restype = C.c_char_p
@@ -153,6 +161,26 @@ def lib():
         L.ani_phase_times.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         _lib = L
     return _lib
+
+
+def formula_string(counts, symbols) -> str:
+    """Formula of a composition in Hill order -- C, then H, then the other symbols alphabetically -- a count of 1 not printed,
+    species with a count of 0 left out: formula_string([4, 1, 0, 0], ["H", "C", "N", "O"]) == "CH4"."""
+    pairs = [(str(sym), int(n)) for sym, n in zip(symbols, counts) if int(n) > 0]
+    pairs.sort(key=lambda p: (0, "") if p[0] == "C" else (1, "") if p[0] == "H" else (2, p[0]))
+    return "".join(sym if n == 1 else f"{sym}{n}" for sym, n in pairs)
+
+
+SUMMARY_KEYS = ("molecules", "compositions", "open_molecules", "bonds", "largest", "open_atoms")
+
+
+def formula_dict(rows, symbols) -> dict:
+    """{formula string: count} of formula rows [n][S + 1] (compositions that print alike are added up)"""
+    out = {}
+    for row in rows:
+        k = formula_string(row[:-1], symbols)
+        out[k] = out.get(k, 0) + int(row[-1])
+    return out
 
 
 class ANI:
@@ -356,6 +384,62 @@ class ANI:
     def stage_ghost_fold(self, d_owner, d_shift, nghost: int):
         """ani_stage_ghost_fold: the fold of the list the NEXT build_list* call builds (checked behind that build's synchronisation)"""
         self._check(self._lib.ani_stage_ghost_fold(self._h, d_owner, d_shift, int(nghost)))
+
+    def species_symbols(self):
+        """the model file's species symbols, in species order (ani_species_symbol)"""
+        return [self._lib.ani_species_symbol(self._h, s).decode() for s in range(self._lib.ani_num_species(self._h))]
+
+    def set_bond_table(self, table):
+        """ani_set_bond_table: an [S][S] array of bond lengths in Angstrom (<= 0: never bonded), or a dict
+        {("H", "O"): 1.16, ...} of unordered symbol pairs (pairs left out are never bonded); None clears the table."""
+        if table is None:
+            self._check(self._lib.ani_set_bond_table(self._h, None, 0))
+            return
+        if isinstance(table, dict):
+            sym = self.species_symbols()
+            t = np.zeros((len(sym), len(sym)))
+            for (a, b), v in table.items():
+                if a not in sym or b not in sym:
+                    raise AniError(f"set_bond_table: the model has no species {a if a not in sym else b!r} (it has {sym})")
+                t[sym.index(a), sym.index(b)] = t[sym.index(b), sym.index(a)] = float(v)
+            table = t
+        t = np.ascontiguousarray(table, dtype=np.float64)
+        if t.ndim != 2 or t.shape[0] != t.shape[1]:
+            raise AniError(f"set_bond_table: a square table is needed, got shape {t.shape}")
+        self._check(self._lib.ani_set_bond_table(self._h, t.ctypes.data, int(t.shape[0])))
+
+    def find_molecules(self, inp_or_x, owner=None, formula_cap: int = 4096, nlocal=None):
+        """ani_find_molecules on the installed list.  inp_or_x: a harness.RankInput (its positions), or an [ntotal, 3] array with
+        ``nlocal`` (default: all of it).  owner: int64 [nghost], the owned atom every ghost stands for (outside [0, nlocal):
+        foreign); None uses an installed ghost fold, or counts every ghost as foreign.  Returns (mol_of_atom [nlocal] int32,
+        {formula string: count} of the closed molecules, summary int64 [6] in the order of SUMMARY_KEYS).  More than formula_cap distinct
+        compositions raise AniError (ANI_ERR_CAPACITY)."""
+        if hasattr(inp_or_x, "nlocal"):
+            x, nl = inp_or_x.x, inp_or_x.nlocal
+        else:
+            x = inp_or_x
+            nl = len(x) if nlocal is None else int(nlocal)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nt = x.shape[0]
+        S = self._lib.ani_num_species(self._h)
+        own = None
+        if owner is not None:
+            own = np.ascontiguousarray(owner, dtype=np.int64)
+            assert own.shape == (nt - nl,)
+        mol = np.full(nl, -1, dtype=np.int32)
+        rows = np.zeros((int(formula_cap), S + 1), dtype=np.int32)
+        summ = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.ani_find_molecules(self._h, nt, nl, x.ctypes.data, own.ctypes.data if own is not None else None,
+                                                 mol.ctypes.data, rows.ctypes.data, int(formula_cap), summ.ctypes.data))
+        return mol, formula_dict(rows[: int(summ[1])], self.species_symbols()), summ
+
+    def find_molecules_device(self, ntotal, nlocal, d_x, d_owner=None, d_mol_of_atom=None, d_formula=None, formula_cap: int = 0,
+                              d_summary=None, stream=None):
+        """ani_find_molecules_device: raw device addresses (e.g. torch tensor .data_ptr()); any output may be None; nothing
+        synchronises.  d_x float64 [ntotal, 3], d_owner int64 [nghost], d_mol_of_atom int32 [nlocal], d_formula int32
+        [formula_cap, S + 1] (rows in unspecified order), d_summary int64 [6]."""
+        self._check(self._lib.ani_find_molecules_device(self._h, int(ntotal), int(nlocal), d_x, d_owner, d_mol_of_atom, d_formula,
+                                                        int(formula_cap), d_summary, stream))
 
     def last_mlp_kernel(self) -> str:
         return self._lib.ani_last_mlp_kernel(self._h).decode()

@@ -193,6 +193,14 @@ struct ani_handle {
   DevBuf<double> dv_stage;       // the host entry points' outputs on the device
   DevBuf<double> dv_part;        // [M][kDevEnergyParts] block partials of member_energy
   DevBuf<unsigned> dv_ticket;    // the closing kernel's ticket (zero between launches)
+  // molecule finder (ani_set_bond_table / ani_find_molecules*): the caller's table squared, scratch of the kernels
+  // (ani_kernels_mol.hip: MolArgs), staging of the host entry
+  bool have_bonds = false;
+  DevBuf<double> bond_cut2;               // [S][S]
+  DevBuf<int> mol_ints;                   // parent | open_atom | open_root | ovf | comp | cnt
+  DevBuf<unsigned long long> mol_words;   // counters | keys
+  DevBuf<long long> mol_owner, mol_summary;
+  DevBuf<int> mol_out;                    // mol_of_atom | formula rows
   int nlocal = 0, ntotal = 0, nrows = 0;
   long long npairs = 0;
   int count[kMaxSpecies] = {0}, row_start[kMaxSpecies] = {0};
@@ -1686,6 +1694,7 @@ void ani_destroy(ani_handle* h) {
   h->avir.release(); h->avir64.release(); h->avout.release();
   h->gaev_parts64.release(); h->dv_fbuf.release(); h->dv_fbuf64.release(); h->dv_tmp.release(); h->dv_stage.release();
   h->dv_part.release(); h->dv_ticket.release();
+  h->bond_cut2.release(); h->mol_ints.release(); h->mol_words.release(); h->mol_owner.release(); h->mol_summary.release(); h->mol_out.release();
   h->virial_acc.release(); h->aev.release(); h->gaev.release(); h->act.release(); h->aev64.release(); h->gaev64.release(); h->act64.release(); h->e_rows64.release(); h->fbuf64.release(); h->e_rows.release(); h->fbuf.release();
   for (int fi = 0; fi < 4; fi++) free_fused(h, fi);
   h->fused_counter.release(); h->gaev_parts.release(); h->fused_sched.release();
@@ -1702,6 +1711,9 @@ int ani_num_species(const ani_handle* h) { return h ? h->model.S : 0; }
 int ani_aev_length(const ani_handle* h) { return h ? h->model.aev_len : 0; }
 double ani_cutoff_radial(const ani_handle* h) { return h ? h->model.Rcr : 0; }
 double ani_cutoff_angular(const ani_handle* h) { return h ? h->model.Rca : 0; }
+const char* ani_species_symbol(const ani_handle* h, int s) {
+  return h && s >= 0 && s < h->model.S ? h->model.symbols[s].c_str() : "";
+}
 
 // ---- per-atom virial (ani_request_atom_virial) ----------------------------------------------------------------
 int ani_request_atom_virial(ani_handle* h, double* out, int ncomp) {
@@ -2378,6 +2390,132 @@ int ani_debug_deviation_parts(ani_handle* h, const void** d_parts, int64_t* memb
   if (!h || !d_parts || !member_stride) return ANI_ERR_ARG;
   *d_parts = h->use_single ? static_cast<const void*>(h->gaev_parts.p) : static_cast<const void*>(h->gaev_parts64.p);
   *member_stride = (int64_t)std::max(h->nrows, 1) * h->ap_run.aev_stride;
+  return ANI_OK;
+}
+
+// ---- molecule finder (ani_set_bond_table, ani_find_molecules*): see include/ani_hip.h ---------------------------------------
+int ani_set_bond_table(ani_handle* h, const double* cut, int nspecies) {
+  if (!h) return ANI_ERR_ARG;
+  if (!cut) { h->have_bonds = false; return ANI_OK; }   // cleared
+  const int S = h->model.S;
+  if (nspecies != S) {
+    h->err = "ani_set_bond_table: nspecies = " + std::to_string(nspecies) + ", the model has " + std::to_string(S) + " species";
+    return ANI_ERR_ARG;
+  }
+  const double rmax = std::min(h->model.Rcr, h->model.Rca);
+  std::vector<double> c2((size_t)S * S);
+  for (int a = 0; a < S; a++)
+    for (int b = 0; b < S; b++) {
+      const double v = cut[a * S + b], w = cut[b * S + a];
+      const std::string pair = "[" + h->model.symbols[a] + "][" + h->model.symbols[b] + "]";
+      if (v != v) { h->err = "ani_set_bond_table: entry " + pair + " is not a number"; return ANI_ERR_ARG; }
+      if (!(v == w) && !(v <= 0 && w <= 0)) { h->err = "ani_set_bond_table: the table is asymmetric at " + pair; return ANI_ERR_ARG; }
+      if (v > rmax) {
+        h->err = "ani_set_bond_table: entry " + pair + " = " + std::to_string(v) + " A is above the cutoff " + std::to_string(rmax) +
+                 " A (the list is only complete inside the force cutoff)";
+        return ANI_ERR_ARG;
+      }
+      c2[(size_t)a * S + b] = v > 0 ? v * v : -1.0;
+    }
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipDeviceSynchronize());   // a call that still reads the table before it is replaced (rare: set-up time)
+  HIP_TRY(h, h->bond_cut2.reserve(c2.size()));
+  HIP_TRY(h, hipMemcpy(h->bond_cut2.p, c2.data(), sizeof(double) * c2.size(), hipMemcpyHostToDevice));
+  h->have_bonds = true;
+  return ANI_OK;
+}
+
+static int find_molecules_args(ani_handle* h, int ntotal, int nlocal, int formula_cap) {
+  if (!h) return ANI_ERR_ARG;
+  if (!h->use_fullnbr) { h->err = "ani_find_molecules: the handle was created for half lists (use_fullnbr = 0)"; return ANI_ERR_ARG; }
+  if (!h->have_bonds) { h->err = "ani_find_molecules: no bond table is set (ani_set_bond_table)"; return ANI_ERR_ARG; }
+  if (!h->have_list) { h->err = "ani_find_molecules: no neighbour list is installed (a call with ago == 0, or ani_build_list*)"; return ANI_ERR_ARG; }
+  if (ntotal != h->ntotal || nlocal != h->nlocal) {
+    h->err = "ani_find_molecules: ntotal / nlocal = " + std::to_string(ntotal) + " / " + std::to_string(nlocal) +
+             " differ from the installed list's " + std::to_string(h->ntotal) + " / " + std::to_string(h->nlocal);
+    return ANI_ERR_ARG;
+  }
+  if (formula_cap < 0) { h->err = "ani_find_molecules: negative formula_cap"; return ANI_ERR_ARG; }
+  if (nlocal >= (1 << 29)) { h->err = "ani_find_molecules: more than 2^29 owned atoms per rank is not supported"; return ANI_ERR_ARG; }
+  return ANI_OK;
+}
+
+int ani_find_molecules_device(ani_handle* h, int ntotal, int nlocal, const double* d_x, const int64_t* d_owner, int* d_mol_of_atom,
+                              int* d_formula, int formula_cap, int64_t* d_summary, void* stream) {
+  const int rc = find_molecules_args(h, ntotal, nlocal, formula_cap);
+  if (rc) return rc;
+  if (!d_x) { h->err = "ani_find_molecules: null positions"; return ANI_ERR_ARG; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int S = h->model.S;
+  MolArgs a{};
+  a.nlocal = nlocal; a.ntotal = ntotal; a.S = S;
+  a.table_size = 64;
+  while (a.table_size < 2 * nlocal) a.table_size *= 2;
+  a.ovf_cap = std::max(nlocal, 1);
+  const size_t n1 = (size_t)std::max(nlocal, 1);
+  HIP_TRY(h, h->mol_ints.reserve(4 * n1 + n1 * S + (size_t)a.table_size));
+  HIP_TRY(h, h->mol_words.reserve((size_t)kMolCounters + (size_t)a.table_size));
+  a.parent = h->mol_ints.p; a.open_atom = a.parent + n1; a.open_root = a.open_atom + n1; a.ovf = a.open_root + n1;
+  a.comp = a.ovf + n1; a.cnt = a.comp + n1 * S;
+  a.counters = h->mol_words.p; a.keys = a.counters + kMolCounters;
+  a.ilist = h->ilist.p; a.nbr_off = h->nbr_off.p; a.numneigh = h->numneigh.p; a.jlist = h->jlist.p; a.species = h->species.p;
+  a.x = d_x; a.cut2 = h->bond_cut2.p;
+  static_assert(sizeof(long long) == sizeof(int64_t), "owner indices are 64-bit");
+  a.owner = d_owner ? reinterpret_cast<const long long*>(d_owner) : (h->fold_nghost >= 0 ? h->fold.owner : nullptr);
+  a.mol_of_atom = d_mol_of_atom; a.formula = d_formula; a.formula_cap = formula_cap;
+  a.summary = reinterpret_cast<long long*>(d_summary);
+  TraceRange tr("ani: molecule finder");
+  launch_find_molecules(a, st);
+  HIP_TRY(h, take_launch_error());
+  return ANI_OK;
+}
+
+int ani_find_molecules(ani_handle* h, int ntotal, int nlocal, const double* coordinates, const int64_t* owner, int* mol_of_atom,
+                       int* formula, int formula_cap, int64_t* summary) {
+  int rc = find_molecules_args(h, ntotal, nlocal, formula_cap);
+  if (rc) return rc;
+  if (!coordinates) { h->err = "ani_find_molecules: null positions"; return ANI_ERR_ARG; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  const int S = h->model.S, W = S + 1, ng = ntotal - nlocal;
+  const size_t nrow = formula ? (size_t)formula_cap : 0;
+  HIP_TRY(h, h->x64.reserve((size_t)std::max(ntotal, 1) * 3));
+  h->x64_from = nullptr;   // the staging array no longer holds what ani_build_list uploaded
+  HIP_TRY(h, hipMemcpyAsync(h->x64.p, coordinates, sizeof(double) * 3 * (size_t)ntotal, hipMemcpyHostToDevice, st));
+  if (owner && ng > 0) {
+    HIP_TRY(h, h->mol_owner.reserve((size_t)ng));
+    HIP_TRY(h, hipMemcpyAsync(h->mol_owner.p, owner, sizeof(int64_t) * (size_t)ng, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(h, h->mol_out.reserve((size_t)std::max(nlocal, 1) + nrow * W));
+  HIP_TRY(h, h->mol_summary.reserve(6));
+  int* d_formula = formula ? h->mol_out.p + std::max(nlocal, 1) : nullptr;
+  rc = ani_find_molecules_device(h, ntotal, nlocal, h->x64.p, owner && ng > 0 ? reinterpret_cast<const int64_t*>(h->mol_owner.p) : nullptr,
+                                 mol_of_atom ? h->mol_out.p : nullptr, d_formula, formula_cap,
+                                 reinterpret_cast<int64_t*>(h->mol_summary.p), st);
+  if (rc) return rc;
+  long long sum[6];
+  if (mol_of_atom && nlocal > 0) HIP_TRY(h, hipMemcpyAsync(mol_of_atom, h->mol_out.p, sizeof(int) * (size_t)nlocal, hipMemcpyDeviceToHost, st));
+  HIP_TRY(h, hipMemcpyAsync(sum, h->mol_summary.p, sizeof(sum), hipMemcpyDeviceToHost, st));
+  HIP_TRY(h, hipStreamSynchronize(st));
+  if (summary) for (int k = 0; k < 6; k++) summary[k] = sum[k];
+  const size_t rows = (size_t)std::min<long long>(sum[1], (long long)nrow);
+  if (rows) {
+    HIP_TRY(h, hipMemcpy(formula, d_formula, sizeof(int) * rows * W, hipMemcpyDeviceToHost));
+    // ascending, lexicographically by composition
+    std::vector<int> order(rows);
+    for (size_t r = 0; r < rows; r++) order[r] = (int)r;
+    std::sort(order.begin(), order.end(), [&](int p, int q) {
+      return std::lexicographical_compare(formula + (size_t)p * W, formula + (size_t)p * W + S, formula + (size_t)q * W, formula + (size_t)q * W + S);
+    });
+    std::vector<int> sorted(rows * W);
+    for (size_t r = 0; r < rows; r++) std::copy(formula + (size_t)order[r] * W, formula + (size_t)order[r] * W + W, sorted.begin() + r * W);
+    std::copy(sorted.begin(), sorted.end(), formula);
+  }
+  if (formula && sum[1] > (long long)formula_cap) {
+    h->err = "ani_find_molecules: " + std::to_string(sum[1]) + " distinct compositions, formula_cap is " + std::to_string(formula_cap);
+    return ANI_ERR_CAPACITY;
+  }
   return ANI_OK;
 }
 

@@ -378,6 +378,40 @@ void launch_dev_close(const DevCloseArgs& a, bool fp64, hipStream_t st);
 // summary[4] = {max d, min d, sum d, max sigma_E} over [0, nlocal) (one block)
 void launch_dev_summary(const double* dd, const double* sig, int nlocal, double* summary, hipStream_t st);
 
+// ---- molecule finder (ani_kernels_mol.hip; ani_find_molecules*, include/ani_hip.h) ----------------------------------------
+enum { MOL_NMOL = 0, MOL_NDISTINCT, MOL_NOPEN, MOL_NBONDS, MOL_LARGEST, MOL_OPEN_ATOMS, MOL_NOVF };
+constexpr int kMolCounters = 8;
+struct MolArgs {
+  int nlocal, ntotal, S;
+  // the installed list: centre ilist[ii] has numneigh[ii] entries from jlist + nbr_off[ii] (dense segments or capacity rows)
+  const int* ilist;
+  const int* nbr_off;
+  const int* numneigh;
+  const int* jlist;
+  const int* species;        // [ntotal] model species
+  const double* x;           // [ntotal*3] the caller's fp64 positions
+  const long long* owner;    // [ntotal - nlocal] owned atom a ghost stands for (outside [0, nlocal): foreign), or NULL: all foreign
+  const double* cut2;        // [S][S] squared bond lengths; <= 0: never bonded
+  // scratch, all (re)initialised by the launch
+  int* parent;               // [nlocal]
+  int* open_atom;            // [nlocal] the centre has a bond to a foreign ghost
+  int* open_root;            // [nlocal] ... some atom of the root's molecule has
+  int* comp;                 // [nlocal][S] composition, filled at the roots
+  unsigned long long* keys;  // [table_size] packed compositions, all ones = empty
+  int* cnt;                  // [table_size] closed molecules of the slot's composition
+  int table_size;            // a power of two, at least 2 nlocal
+  int* ovf;                  // [ovf_cap] roots of the closed molecules whose composition does not fit a key
+  int ovf_cap;
+  unsigned long long* counters;   // [kMolCounters] indexed by MOL_*
+  // outputs, each may be NULL
+  int* mol_of_atom;          // [nlocal]
+  int* formula;              // [formula_cap][S + 1]
+  int formula_cap;
+  long long* summary;        // [6]
+};
+// six launches on st, nothing waits: see ani_kernels_mol.hip
+void launch_find_molecules(const MolArgs& a, hipStream_t st);
+
 // ---- double precision path (ani_kernels_f64.hip) ------------------------------------------------------------
 struct Aev64Params {
   int S, nR, nA, nZ, radial_len, aev_len, aev_stride, compat;

@@ -507,6 +507,34 @@ class VerletRun:
         d2 = torch.where(torch.isfinite(self.ev[:1]), d2, torch.full_like(d2, float("inf")))
         self._allreduce_max(d2.clone())
 
+    # ---- analysis ----------------------------------------------------------------------------------------
+    def find_molecules(self, formula_cap: int = 4096):
+        """Which molecules are in the box now (ani_find_molecules_device, include/ani_hip.h; the handle needs a bond table:
+        ``ani.set_bond_table``): the loop's own positions, the installed list and the owner maps of its ghost shell, on the loop's
+        stream.  Returns (mol_of_atom [nlocal] int32, {formula string: count}, summary int64 [6]) like ANI.find_molecules.  One
+        rank only: merging the open molecules of several ranks is not done here (the summary's open counts are what such an
+        exchange would start from)."""
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.find_molecules: one rank only (molecules that cross ranks are not merged)")
+        from .ani_hip import AniError, formula_dict
+        n, ng, st = self.nlocal, self.ntotal - self.nlocal, self._stream
+        owner = self.dc.send_idx
+        if ng and self._fused:
+            # the ghost rows of x as images of the owned atoms' positions of this moment (a step's first kernel does the same)
+            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), owner.data_ptr(), self.dc.send_shift.data_ptr(), n, ng, st))
+        elif ng:
+            self.dc.forward_positions(self.x)
+        S = len(self.ani.species_symbols())
+        mol = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        rows = torch.zeros((int(formula_cap), S + 1), dtype=torch.int32, device=self.device)
+        summ = torch.zeros(6, dtype=torch.int64, device=self.device)
+        self.ani.find_molecules_device(self.ntotal, n, self.x.data_ptr(), owner.data_ptr() if ng else None, mol.data_ptr(),
+                                       rows.data_ptr(), int(formula_cap), summ.data_ptr(), stream=st)
+        summ = summ.cpu().numpy()
+        if summ[1] > formula_cap:
+            raise AniError(f"find_molecules: {int(summ[1])} distinct compositions, formula_cap is {formula_cap}")
+        return mol[:n].cpu().numpy(), formula_dict(rows[: int(summ[1])].cpu().numpy(), self.ani.species_symbols()), summ
+
     # ---- thermo ------------------------------------------------------------------------------------------
     def kinetic_energy(self) -> float:
         ke = 0.5 * MVV2E * (self.mass * self.v.square()).sum().reshape(1)
