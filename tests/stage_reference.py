@@ -102,6 +102,19 @@ def full_width_rows(ani, nlocal):
     return full, rows, v, cm
 
 
+def full_width_gaev(ani, nlocal):
+    """The kernel's dE/dAEV rows (``d_gaev``), one per centre (in centre order), at the model's full AEV width: rows through
+    ``d_row_of_centre``, columns through ``colmap()``.  The columns of absent species, which the kernels do not hold, are zero:
+    no neighbour contributes to them, so they carry no force.  This is what ``Oracle.aev_vjp`` takes."""
+    v = ani.debug_view()
+    A = v.aev_active_length
+    rows = ani.debug_read(v.d_row_of_centre, (nlocal,), np.int32)
+    g = ani.debug_read(v.d_gaev, (v.nrows, v.aev_stride), np.float32)
+    full = np.zeros((nlocal, ani.aev_length), np.float64)
+    full[:, ani.colmap()] = g[rows, :A]
+    return full
+
+
 def _celu(z, alpha):
     return np.where(z > 0, z, alpha * np.expm1(np.minimum(z, 0) / alpha))
 
