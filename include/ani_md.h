@@ -75,6 +75,58 @@ int ani_md_ghost_shell_fill(const double* x, int n, const double* clo, const dou
 int ani_md_append_ghosts(double* x, int* species, int nlocal, const int64_t* owner, const double* shift, int nghost, void* stream);
 int ani_md_check(double* d2max, const double* ev, double* out, void* stream);
 
+/*
+ * FIRE energy minimisation in the loop (LAMMPS `min_style fire`; Guenole et al., Comput. Mater. Sci. 175 (2020) 109584): an
+ * integrator with three global dot products and a handful of scalars, all of it on the device.  The host looks at the state
+ * record only where it looks anyway (the re-neighbouring decision).
+ *
+ * Parameters: the defaults of LAMMPS `min_modify` are dtmax = 10 dt0, dtmin = 0.02 dt0, dtgrow 1.1, dtshrink 0.5, alpha0 0.25,
+ * alphashrink 0.99, delaystep 20, initialdelay 1, halfstepback 1, dmax 0.1 A; dt0, etol, ftol and maxiter are the caller's.
+ *
+ * State: ANI_MD_FIRE_NSTATE doubles on the device, read by the host after a synchronisation:
+ *   [0] iterations done   [1] dt   [2] alpha   [3] last_negative   [4] e_prev   [5] e_cur
+ *   [6] P = sum v.f   [7] vv = sum v.v   [8] ff = sum f.f   (of the last iteration that was not frozen)
+ *   [9] dtv of the last move   [10] uphill events   [11] dmax-limited moves
+ *   [12] stop: 0 running, 1 etol, 2 ftol, 3 maxiter, 4 non-finite energy or force norm
+ *   [13] energy and [14] ff of the start point (seen by iteration 1)   [15] largest |velocity component| of the last move
+ *
+ * ani_md_fire_init       fills the record (dt = dt0, alpha = alpha0, everything else 0) and zeroes v[nlocal][3].
+ * ani_md_fire_work_size  doubles of scratch that ani_md_fire_iterate needs for nlocal atoms (no initialisation needed; the same
+ *                        buffer through all iterations of a minimisation).
+ * ani_md_fire_iterate    iteration k = iterations done + 1 on the nlocal owned atoms, from x, v, f = F(x) and E = ev[0] of the last
+ *                        force evaluation; fm[i] = ftm2v / mass_i.  Three launches (reduce, velocity, move):
+ *   1. P, vv, ff: per-block partials, then a sum over the partials, both in a fixed order -- no floating-point atomics, so the
+ *      same inputs give bitwise the same sums in every launch (the branch below hangs on the sign of P).
+ *   2. stop != 0: nothing at all is written -- not x, not v, not the state.  A host that looks every few iterations still finds the
+ *      exact iteration and the exact point of the stop.
+ *   3. stopping tests on the current point, in this order: E or ff not finite -> 4;  ff < ftol^2 -> 2;  k > 1 and
+ *      (k - 1 - last_negative) > delaystep and |E - e_prev| < etol * 0.5 * (|E| + |e_prev| + 1e-8) -> 1;  iterations done == maxiter -> 3.
+ *      A test that fires sets stop, records E, P, vv, ff of the point it stopped on, and ends the iteration: no move, and
+ *      iterations done, dt, alpha, e_prev stay.
+ *   4. P > 0:  s1 = 1 - alpha;  s2 = ff <= 1e-20 ? 0 : alpha sqrt(vv / ff);  then, if k - last_negative > delaystep:
+ *      dt = min(dt dtgrow, dtmax), alpha *= alphashrink.
+ *   5. P <= 0 (an uphill event, the exact zero of a start from rest included):  last_negative = k;  unless (initialdelay and
+ *      k <= delaystep): alpha = alpha0 and dt *= dtshrink if that stays >= dtmin;  with halfstepback x -= 0.5 dtv_prev v, where
+ *      dtv_prev is the dtv of the move before;  v = 0.
+ *   6. v += dt fm[i] f;  if P > 0: v = s1 v + s2 f;  vmax = largest |component| of any v;  dtv = dt, or dmax / vmax when
+ *      dtv vmax > dmax (a limited move);  x += dtv v;  *d2max = max(*d2max, |x_i - x_built_i|^2) as ani_md_initial_integrate
+ *      (x_built or d2max NULL: skipped).
+ *   7. iterations done = k, e_prev = e_cur = E.
+ * ani_md_fire_check      ani_md_check with the state record behind it: out[0] as there, out[1 + j] = state[j]
+ *                        (out: 1 + ANI_MD_FIRE_NSTATE doubles).
+ */
+#define ANI_MD_FIRE_NSTATE 16
+typedef struct ani_md_fire_params {
+  double dt0, dtmax, dtmin, dtgrow, dtshrink, alpha0, alphashrink, dmax, etol, ftol;
+  int delaystep, initialdelay, halfstepback, maxiter;
+} ani_md_fire_params;
+int ani_md_fire_work_size(int nlocal);
+int ani_md_fire_init(double* state, double* v, int nlocal, const ani_md_fire_params* p, void* stream);
+int ani_md_fire_iterate(double* x, double* v, const double* f, const double* fm, int nlocal, const double* ev,
+                        const ani_md_fire_params* p, double* state, double* work, const double* x_built, double* d2max,
+                        void* stream);
+int ani_md_fire_check(double* d2max, const double* ev, const double* state, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,32 @@ class DebugView(C.Structure):
                 ("species_count", C.c_int * 16), ("aev_stride", C.c_int), ("aev_active_length", C.c_int), ("error_flags", C.c_int)]
 
 
+class FireParams(C.Structure):
+    """ani_md_fire_params of include/ani_md.h"""
+    _fields_ = [(n, C.c_double) for n in ("dt0", "dtmax", "dtmin", "dtgrow", "dtshrink", "alpha0", "alphashrink", "dmax", "etol",
+                                          "ftol")] + [(n, C.c_int) for n in ("delaystep", "initialdelay", "halfstepback", "maxiter")]
+
+
+FIRE_NSTATE = 16
+FIRE_STATE_KEYS = ("iterations", "dt", "alpha", "last_negative", "e_prev", "e_cur", "P", "vv", "ff", "dtv", "uphill", "limited", "stop",
+                   "e_first", "ff_first", "vmax")
+FIRE_STOP_REASONS = ("running", "etol", "ftol", "maxiter", "non-finite")
+
+
+def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
+    """ani_md_fire_params with the defaults of LAMMPS `min_modify` (dtmax = 10 dt0, dtmin = 0.02 dt0, ...); kw overrides them"""
+    vals = dict(dt0=float(dt0), dtmax=10.0 * dt0, dtmin=0.02 * dt0, dtgrow=1.1, dtshrink=0.5, alpha0=0.25, alphashrink=0.99,
+                dmax=0.1, etol=float(etol), ftol=float(ftol), delaystep=20, initialdelay=1, halfstepback=1, maxiter=int(maxiter))
+    unknown = set(kw) - set(vals)
+    if unknown:
+        raise TypeError(f"unknown FIRE parameter(s): {sorted(unknown)}")
+    vals.update(kw)
+    p = FireParams()
+    for name, ctype in FireParams._fields_:
+        setattr(p, name, int(vals[name]) if ctype is C.c_int else float(vals[name]))
+    return p
+
+
 def build(force: bool = False) -> str:
     """Compile libani_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).  force: rebuild every object
     (make -B) whatever the timestamps say.  Returns the library path; build.last_commands holds the compiler command
@@ -132,6 +158,11 @@ def lib():
         L.ani_md_reverse_ghosts_ordered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.ani_md_pack_ghosts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ani_md_unpack_reverse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_md_fire_work_size.argtypes = [C.c_int]
+        L.ani_md_fire_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(FireParams), C.c_void_p]
+        L.ani_md_fire_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FireParams),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_fire_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

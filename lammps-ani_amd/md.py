@@ -368,6 +368,10 @@ class VerletRun:
                     raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
                                        "capacity (ANI_ERR_CAPACITY) or the forces diverged")
                 rebuild = worst > (0.5 * self.skin) ** 2
+        self._ghosts_and_forces(rebuild)
+
+    def _ghosts_and_forces(self, rebuild: bool):
+        """re-neighbouring or forward ghost positions, then forces and reverse ghost forces, by whichever path the loop is on"""
         if rebuild:
             self._build_list()
         elif self._overlap:
@@ -424,6 +428,74 @@ class VerletRun:
                     self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.dt, self.nlocal,
                     1 if lang else 0, self._g1.data_ptr() if lang else None, self._g2.data_ptr() if lang else None,
                     self.tag.data_ptr(), self._seed, self.step_no, self.x_built.data_ptr(), self._d2max.data_ptr(), self._stream))
+
+    def minimize(self, etol: float, ftol: float, maxiter: int, dt0=None, check_every=None, on_look=None, **fire_params):
+        """``min_style fire`` + ``minimize etol ftol maxiter``: FIRE energy minimisation of the owned atoms without leaving the
+        device (ani_md_fire_*, include/ani_md.h).  Velocities are zeroed, then every iteration is the three FIRE launches, ghost
+        positions, ani_compute_full_device and ghost forces on the paths of ``run`` (ghost fold, native re-neighbouring,
+        device_overwrite_forces).  The optimiser's whole state lives in a device record; the host looks every `check_every`
+        iterations (default: the loop's `every`) with the one pinned read of the displacement check, which brings the record
+        along: it rebuilds the list when an atom has moved more than skin/2, stops when the record says so, and raises on a
+        non-finite energy.  A stopped record freezes x, v and itself, so the result does not depend on `check_every`.
+        dt0: first timestep in fs (default: the loop's dt); fire_params: dtmax, dtmin, dtgrow, dtshrink, alpha0, alphashrink,
+        delaystep, initialdelay, halfstepback, dmax (defaults of LAMMPS ``min_modify``, ani_hip.fire_params); on_look: optional
+        callable(state dict) at every look of the host, before a rebuild.
+        Returns a dict: iterations, stop (etol / ftol / maxiter), energy_before / energy_after, fnorm_before / fnorm_after
+        (sqrt(sum f.f) over the owned atoms), force_evaluations, uphill_events, limited_moves, rebuilds.
+        On return v is zero, the forces belong to the positions, step_no and the Langevin stream are untouched: ``run`` can follow.
+        One rank only: with several, the three sums of an iteration would need an all-reduce each (open lead)."""
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.minimize: one rank only (the sums of an iteration are not reduced over ranks)")
+        if not self._native_rebuild:
+            raise RuntimeError("VerletRun.minimize needs the device loop with native re-neighbouring (one rank on the GPU)")
+        from . import ani_hip
+        md, st, n = self._md, self._stream, self.nlocal
+        maxiter = int(maxiter)
+        every = self.every if check_every is None else int(check_every)
+        if every < 1 or maxiter < 0:
+            raise ValueError("VerletRun.minimize: check_every >= 1 and maxiter >= 0")
+        par = ani_hip.fire_params(self.dt if dt0 is None else dt0, etol, ftol, maxiter, **fire_params)
+        ns = ani_hip.FIRE_NSTATE
+        state = torch.zeros(ns, dtype=torch.float64, device=self.device)
+        work = torch.empty(md.ani_md_fire_work_size(n), dtype=torch.float64, device=self.device)
+        chk_dev = torch.zeros(1 + ns, dtype=torch.float64, device=self.device)
+        chk_host = torch.zeros(1 + ns, dtype=torch.float64).pin_memory()
+        fm = FTM2V / self.mass[:, 0].contiguous()
+        self._check(md.ani_md_fire_init(state.data_ptr(), self.v.data_ptr(), n, par, st))
+        builds0 = self.nbuilds
+        # the forces of the start point: those in f may carry the thermostat's term of the last step
+        self._ghosts_and_forces(False)
+        nevals, calls = 1, 0
+        while True:
+            self._check(md.ani_md_fire_iterate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), fm.data_ptr(), n,
+                                               self.ev.data_ptr(), par, state.data_ptr(), work.data_ptr(),
+                                               self.x_built.data_ptr(), self._d2max.data_ptr(), st))
+            calls += 1
+            self.since_build += 1
+            rebuild = False
+            # the stop by maxiter falls in call maxiter + 1 at the latest: that look ends the loop whatever check_every is
+            if calls % every == 0 or calls == maxiter + 1:
+                self._check(md.ani_md_fire_check(self._d2max.data_ptr(), self.ev.data_ptr(), state.data_ptr(), chk_dev.data_ptr(), st))
+                chk_host.copy_(chk_dev, non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+                worst = float(chk_host[0])
+                rec = dict(zip(ani_hip.FIRE_STATE_KEYS, chk_host[1:].tolist()))
+                if on_look is not None:
+                    on_look(rec)
+                if worst == float("inf") or rec["stop"] == 4.0:
+                    self.v.zero_()
+                    raise RuntimeError("non-finite energy or force norm in VerletRun.minimize: a neighbour count exceeded the "
+                                       "kernels' LDS capacity (ANI_ERR_CAPACITY) or the forces diverged")
+                if rec["stop"] != 0.0:
+                    break
+                rebuild = worst > (0.5 * self.skin) ** 2
+            self._ghosts_and_forces(rebuild)
+            nevals += 1
+        self.v.zero_()
+        return dict(iterations=int(rec["iterations"]), stop=ani_hip.FIRE_STOP_REASONS[int(rec["stop"])],
+                    energy_before=rec["e_first"], energy_after=rec["e_cur"], fnorm_before=rec["ff_first"] ** 0.5,
+                    fnorm_after=rec["ff"] ** 0.5, force_evaluations=nevals, uphill_events=int(rec["uphill"]),
+                    limited_moves=int(rec["limited"]), rebuilds=self.nbuilds - builds0)
 
     def _pack_and_send_ghosts(self):
         """forward exchange on the current stream: x[nlocal:] <- the owners' positions (+ image shifts)"""
