@@ -127,6 +127,54 @@ int ani_md_fire_iterate(double* x, double* v, const double* f, const double* fm,
                         void* stream);
 int ani_md_fire_check(double* d2max, const double* ev, const double* state, double* out, void* stream);
 
+/*
+ * Holonomic bond-length constraints in the loop, in the RATTLE form (Andersen, J. Comput. Phys. 52 (1983) 24; LAMMPS `fix shake`
+ * / `fix rattle` on clusters of 2, 3 and 4 atoms): one central atom and one to three partners, every constrained bond joins the
+ * centre to a partner.  Two stages per step, each one launch behind a kernel of the integrator; a loop without constraints
+ * launches neither.
+ *
+ * Shared inputs:
+ *   cl[nc][4]      int32: the centre and up to three partners as local indices (< nlocal), -1 for an unused slot; the used slots
+ *                  come first, and no atom belongs to two clusters.  A wave runs one cluster size when the table is ordered by size.
+ *   d[nc][3]       the bond lengths in A (slot k of d belongs to slot 1 + k of cl; unused slots are not read)
+ *   w[nlocal]      any array proportional to 1 / mass_i (the loop passes its dtfm)
+ *   len3, periodic_mask   as ani_md_wrap_positions (host pointer to three doubles): every bond vector is a minimum image,
+ *                  minimg(a)[k] = a[k] - len3[k] rint(a[k] / len3[k]) in the periodic dimensions -- the loop wraps owned atoms at a
+ *                  rebuild, so a cluster can sit across a face.
+ *
+ * ani_md_shake_positions   after ani_md_initial_integrate: x holds the unconstrained x', v the half-step velocity.  The old
+ *   positions are rebuilt as x0 = x' - dt v (no copy is kept).  With s_k = minimg(x0_c - x0_pk) it finds g_k such that
+ *       x_c = x'_c + w_c sum_k g_k s_k,   x_pk = x'_pk - w_pk g_k s_k,   | |r_k|^2 - d_k^2 | <= tol d_k^2  for every k,
+ *   r_k = minimg(x_c - x_pk), by Newton on the K <= 3 unknowns from g = 0, the K x K Jacobian solved directly, at most maxiter
+ *   iterations (an iteration is one solve; the test comes first, so a start that holds takes none and moves nothing).  Then
+ *   v_i += (x_i - x'_i) / dt, and |x_i - x_built_i|^2 of the moved atoms is folded into *d2max as ani_md_initial_integrate does
+ *   it (a workgroup maximum, then at most one integer atomic on the bit pattern; x_built or d2max NULL: skipped).
+ *   v == NULL: x0 = x' and no velocity is written -- the form that projects a start configuration onto the constraints.
+ *   A cluster that reaches maxiter unconverged is written with what it has, and counted.
+ *
+ * ani_md_rattle_velocities  after ani_md_final_integrate: with r_k = minimg(x_c - x_pk) of the current positions it finds h_k
+ *   such that
+ *       v_c += w_c sum_k h_k r_k,   v_pk -= w_pk h_k r_k,   r_k . (v_c - v_pk) = 0  for every k:
+ *   a symmetric positive-definite K x K linear system, solved directly, no iteration.  d is not read (the constraint is on the
+ *   direction of the bond as it is); the argument keeps the two stages' shared inputs in one shape.
+ *
+ * stats: ANI_MD_SHAKE_NSTATS `unsigned long long` words on the device, zeroed by the caller (NULL: not kept):
+ *   [0] clusters that reached maxiter unconverged (accumulates over the calls)   [1] the largest iteration count
+ *   [2] the largest final relative residual max_k | |r_k|^2 - d_k^2 | / d_k^2, as the bit pattern of a non-negative double
+ *       (a NaN orders above every finite pattern: a blown-up cluster shows here)   [3] calls
+ *   updated with integer atomics only, after a workgroup reduction.
+ *
+ * Both kernels: one thread per cluster, 256-thread blocks, everything in registers; no floating-point atomics anywhere, so the
+ * same inputs give bitwise the same outputs; atoms in no cluster are not written.  The momentum of a cluster is conserved
+ * (sum_i dx_i / w_i = 0, sum_i dv_i / w_i = 0).
+ */
+#define ANI_MD_SHAKE_NSTATS 4
+int ani_md_shake_positions(double* x, double* v, const int* cl, const double* d, int nc, const double* w, double dt, double tol,
+                           int maxiter, const double* len3, int periodic_mask, const double* x_built, double* d2max,
+                           unsigned long long* stats, void* stream);
+int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const double* d, int nc, const double* w,
+                             const double* len3, int periodic_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

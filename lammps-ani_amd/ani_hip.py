@@ -52,6 +52,9 @@ FIRE_NSTATE = 16
 FIRE_STATE_KEYS = ("iterations", "dt", "alpha", "last_negative", "e_prev", "e_cur", "P", "vv", "ff", "dtv", "uphill", "limited", "stop",
                    "e_first", "ff_first", "vmax")
 FIRE_STOP_REASONS = ("running", "etol", "ftol", "maxiter", "non-finite")
+# ANI_MD_SHAKE_NSTATS words of include/ani_md.h (ani_md_shake_positions): the third is the bit pattern of a double
+SHAKE_NSTATS = 4
+SHAKE_STATS_KEYS = ("unconverged", "max_iterations", "max_residual", "calls")
 
 
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
@@ -163,6 +166,10 @@ def lib():
         L.ani_md_fire_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FireParams),
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ani_md_fire_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_shake_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double,
+                                             C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_rattle_velocities.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

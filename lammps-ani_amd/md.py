@@ -34,6 +34,54 @@ BOLTZ = 0.0019872067
 ANI2X_MASSES = (1.008, 12.011, 14.007, 15.999, 32.06, 18.998, 35.45)
 
 
+def constraint_clusters(bonds, tags):
+    """The clusters of ``VerletRun.set_constraints`` (LAMMPS FixShake::find_clusters, without its angle form): every connected
+    component of the constrained bonds has to be a star -- one centre bonded to one, two or three partners that have no other
+    constrained bond.  bonds: [nb, 2] global tags; tags: [nlocal], the global tag of every local index.
+    Returns (cl [nc, 4] int32: centre and partners as local indices, -1 in unused slots; slot_bond [nc, 3] int64: which row of
+    `bonds` slot k is, -1 unused), clusters ordered by size, then by centre index, the partners of a centre ascending.  A
+    two-atom component takes its lower local index as the centre.  Raises ValueError naming the offending tag for an unknown
+    tag, a self-bond, a duplicate bond, a component that is not a star and a centre with more than three partners."""
+    bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+    tags = np.asarray(tags, dtype=np.int64).reshape(-1)
+    local = {int(t): i for i, t in enumerate(tags.tolist())}
+    seen, nbrs = set(), {}
+    for b, (ta, tb) in enumerate(bonds.tolist()):
+        for t in (ta, tb):
+            if t not in local:
+                raise ValueError(f"constraint bond {b} ({ta}, {tb}): unknown tag {t}")
+        if ta == tb:
+            raise ValueError(f"constraint bond {b}: self-bond on tag {ta}")
+        key = (min(ta, tb), max(ta, tb))
+        if key in seen:
+            raise ValueError(f"constraint bond {b}: duplicate of the bond between tags {key[0]} and {key[1]}")
+        seen.add(key)
+        nbrs.setdefault(local[ta], []).append((local[tb], b))
+        nbrs.setdefault(local[tb], []).append((local[ta], b))
+    found = []
+    for i, nb in nbrs.items():
+        if len(nb) == 1:
+            j, b = nb[0]
+            if len(nbrs[j]) == 1 and i < j:
+                found.append((i, nb))
+            continue
+        for j, _ in nb:
+            if len(nbrs[j]) > 1:
+                raise ValueError(f"constraint clusters: the component of tag {int(tags[i])} is not a star (tag {int(tags[i])} and its "
+                                 f"partner tag {int(tags[j])} both have further constrained bonds)")
+        if len(nb) > 3:
+            raise ValueError(f"constraint clusters: tag {int(tags[i])} is the centre of {len(nb)} constrained bonds (at most 3)")
+        found.append((i, sorted(nb)))
+    found.sort(key=lambda c: (len(c[1]), c[0]))
+    cl = np.full((len(found), 4), -1, dtype=np.int32)
+    slot_bond = np.full((len(found), 3), -1, dtype=np.int64)
+    for c, (i, nb) in enumerate(found):
+        cl[c, 0] = i
+        for k, (j, b) in enumerate(nb):
+            cl[c, 1 + k], slot_bond[c, k] = j, b
+    return cl, slot_bond
+
+
 class VerletRun:
     def __init__(self, ani, inp, box_len, device, dt: float = 0.5, cutoff: float = 5.1, skin: float = 2.0,
                  ghost_margin: float = 0.0, every: int = 10, masses=ANI2X_MASSES, group=None, seed: int = 12345,
@@ -103,6 +151,8 @@ class VerletRun:
         self._native_rebuild = bool(self._fused and not self.dc.multi and
                                     os.environ.get("ANI_MD_NATIVE_REBUILD", "1") not in ("", "0"))
         self._cap = 0
+        self._cons = None      # bond constraints (set_constraints): None, or the device tables and parameters of the two stages
+        self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
             self._comm_stream = torch.cuda.current_stream(device) if os.environ.get("ANI_MD_OVERLAP_ONE_STREAM") else \
@@ -308,9 +358,11 @@ class VerletRun:
             pm = pm.to(self.device)
             p, mtot = pm[:3], pm[3:]
         self.v -= p / mtot
+        if self._cons is not None:
+            self.project_velocities()   # the components along the constrained bonds carry no temperature: out before the rescale
         ke = self.kinetic_energy()
         n = self._allreduce_sum(torch.tensor([float(self.nlocal)], dtype=torch.float64, device=self.device))
-        t_now = 2.0 * ke / (3.0 * n - 3.0) / BOLTZ
+        t_now = 2.0 * ke / (3.0 * n - 3.0 - self._ncons) / BOLTZ
         self.v *= (T / t_now) ** 0.5
 
     def _allreduce_sum(self, t: torch.Tensor) -> float:
@@ -351,6 +403,8 @@ class VerletRun:
                 if worst == float("inf"):
                     raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
                                        "capacity (ANI_ERR_CAPACITY) or the forces diverged")
+                if self._cons is not None:
+                    self._constraint_health(self._chk_host[1:])   # the stats words sit behind the maximum: the same read
                 rebuild = worst > (0.5 * self.skin) ** 2
                 d2 = None
             elif self._fused:
@@ -399,8 +453,12 @@ class VerletRun:
     def step(self, force_rebuild: bool = False):
         """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements)"""
         self._initial_integrate()
+        if self._cons is not None:
+            self._shake_positions()
         self._middle(force_rebuild)
         self._final_integrate()
+        if self._cons is not None:
+            self.project_velocities()
 
     def run(self, nsteps: int, before_forces=None, after_forces=None):
         """``run N`` without per-step output: nothing looks at the full-step velocities between two steps, so the
@@ -413,14 +471,24 @@ class VerletRun:
             for _ in range(nsteps):
                 self.step()
             return
+        cons = self._cons is not None
         self._initial_integrate()
+        if cons:
+            self._shake_positions()
         for k in range(nsteps):
             if before_forces is not None:
                 before_forces(k)
             self._middle()
             if after_forces is not None:
                 after_forces(k)
-            if k + 1 == nsteps:
+            if cons:
+                # the velocity stage stands between the two halves: the separate launches of step(), same arithmetic
+                self._final_integrate()
+                self.project_velocities()
+                if k + 1 < nsteps:
+                    self._initial_integrate()
+                    self._shake_positions()
+            elif k + 1 == nsteps:
                 self._final_integrate()
             else:
                 lang = self._g1 is not None
@@ -448,6 +516,9 @@ class VerletRun:
             raise RuntimeError("VerletRun.minimize: one rank only (the sums of an iteration are not reduced over ranks)")
         if not self._native_rebuild:
             raise RuntimeError("VerletRun.minimize needs the device loop with native re-neighbouring (one rank on the GPU)")
+        if self._cons is not None:
+            raise RuntimeError("VerletRun.minimize: bond constraints are set (LAMMPS turns SHAKE into restraints during a "
+                               "minimisation; that is not built) -- clear them with set_constraints([]) first")
         from . import ani_hip
         md, st, n = self._md, self._stream, self.nlocal
         maxiter = int(maxiter)
@@ -496,6 +567,100 @@ class VerletRun:
                     energy_before=rec["e_first"], energy_after=rec["e_cur"], fnorm_before=rec["ff_first"] ** 0.5,
                     fnorm_after=rec["ff"] ** 0.5, force_evaluations=nevals, uphill_events=int(rec["uphill"]),
                     limited_moves=int(rec["limited"]), rebuilds=self.nbuilds - builds0)
+
+    # ---- bond constraints ----------------------------------------------------------------------------------
+    def set_constraints(self, bonds, lengths=None, tol: float = 1e-10, maxiter: int = 20, project: bool = True):
+        """``fix shake`` / ``fix rattle`` on bonds: holonomic bond-length constraints in the RATTLE form (ani_md_shake_positions /
+        ani_md_rattle_velocities, include/ani_md.h).  bonds: [nb, 2] global tags; lengths: [nb] in A (None: the current
+        minimum-image distances); tol: bound on | |r|^2 - d^2 | / d^2 of every bond after the position stage; maxiter: Newton
+        iterations per cluster and step.  The host builds the clusters (``constraint_clusters``: stars of a centre and one to
+        three partners, ValueError otherwise).  From here on step() runs initial, position stage, forces, final, velocity stage
+        and run() makes the same launches; every look of the host (the displacement check) brings the stage's statistics along
+        and raises when a cluster did not converge.  project: run the position stage once on the positions as they are (old and
+        new positions the same, no velocity written), then the velocity stage, and -- with lengths given, which moves atoms --
+        evaluate the forces again.  An empty bond list clears the constraints: the loop launches what it launched before.
+        temperature() and create_velocities count 3 N - 3 - nb degrees of freedom.  One rank with native re-neighbouring only
+        (the owned atoms keep their order there, so the cluster table stays valid across rebuilds)."""
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.set_constraints: one rank only (a cluster's atoms would have to migrate together)")
+        if not self._native_rebuild:
+            raise RuntimeError("VerletRun.set_constraints needs the device loop with native re-neighbouring (one rank on the GPU)")
+        from . import ani_hip
+        bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+        nb = int(bonds.shape[0])
+        if nb == 0:
+            self._cons, self._ncons = None, 0
+            return
+        if not (tol > 0.0) or int(maxiter) < 1:
+            raise ValueError("VerletRun.set_constraints: tol > 0 and maxiter >= 1")
+        n = self.nlocal
+        cl, slot = constraint_clusters(bonds, self.tag.cpu().numpy())
+        used = slot >= 0
+        if lengths is None:
+            x = self.x[:n].cpu().numpy()
+            dv = x[np.repeat(cl[:, :1], 3, 1)[used]] - x[cl[:, 1:][used]]
+            for k in range(3):
+                if self.dc.periodic[k]:
+                    dv[:, k] -= self._box_len_np[k] * np.round(dv[:, k] / self._box_len_np[k])
+            dused = np.sqrt((dv * dv).sum(1))
+        else:
+            blen = np.asarray(lengths, dtype=np.float64).reshape(-1)
+            if blen.shape[0] != nb:
+                raise ValueError(f"VerletRun.set_constraints: {nb} bonds but {blen.shape[0]} lengths")
+            dused = blen[slot[used]]
+        if not (np.isfinite(dused).all() and (dused > 0.0).all()):
+            raise ValueError("VerletRun.set_constraints: bond lengths must be positive and finite")
+        d = np.zeros((cl.shape[0], 3))
+        d[used] = dused
+        # the statistics sit behind the word of the displacement check: one pinned read of a look brings both
+        ns = ani_hip.SHAKE_NSTATS
+        self._chk_dev = torch.zeros(1 + ns, dtype=torch.float64, device=self.device)
+        self._chk_host = torch.zeros(1 + ns, dtype=torch.float64).pin_memory()
+        self._cons = dict(cl=torch.as_tensor(cl, device=self.device).contiguous(), d=torch.as_tensor(d, device=self.device).contiguous(),
+                          nc=int(cl.shape[0]), tol=float(tol), maxiter=int(maxiter), stats=self._chk_dev[1:])
+        self._ncons = nb
+        if project:
+            self._shake_positions(with_velocities=False)
+            self.project_velocities()
+            self._constraint_health(self._chk_dev[1:].cpu())
+            if lengths is not None:
+                self._ghosts_and_forces(False)   # the forces of the projected positions
+
+    def _shake_positions(self, with_velocities: bool = True):
+        c = self._cons
+        self._check(self._md.ani_md_shake_positions(self.x.data_ptr(), self.v.data_ptr() if with_velocities else None, c["cl"].data_ptr(),
+                                                    c["d"].data_ptr(), c["nc"], self._dtfm1.data_ptr(), self.dt, c["tol"], c["maxiter"],
+                                                    self._len3.ctypes.data, self._pmask, self.x_built.data_ptr(),
+                                                    self._d2max.data_ptr(), c["stats"].data_ptr(), self._stream))
+
+    def project_velocities(self):
+        """the velocity stage on the current v: the components along the constrained bonds are taken out (``fix rattle``'s
+        half; after velocities were set by hand).  Nothing to do without constraints."""
+        c = self._cons
+        if c is None:
+            return
+        self._check(self._md.ani_md_rattle_velocities(self.x.data_ptr(), self.v.data_ptr(), c["cl"].data_ptr(), c["d"].data_ptr(), c["nc"],
+                                                      self._dtfm1.data_ptr(), self._len3.ctypes.data, self._pmask, self._stream))
+
+    @staticmethod
+    def _stats_record(words) -> dict:
+        """the ANI_MD_SHAKE_NSTATS words (a float64 tensor on the host that carries their bit patterns) as a dict"""
+        u = words.numpy().view(np.uint64)
+        return dict(unconverged=int(u[0]), max_iterations=int(u[1]), max_residual=float(u[2:3].view(np.float64)[0]), calls=int(u[3]))
+
+    def _constraint_health(self, words):
+        rec = self._stats_record(words)
+        if rec["unconverged"] != 0 or not np.isfinite(rec["max_residual"]):
+            raise RuntimeError(f"bond constraints: {rec['unconverged']} cluster solve(s) reached maxiter = {self._cons['maxiter']} "
+                               f"unconverged; largest relative residual {rec['max_residual']:.3e} (tol {self._cons['tol']:.1e}) "
+                               f"over {rec['calls']} calls")
+
+    def constraint_stats(self) -> dict:
+        """the record of the position stage since set_constraints: unconverged (cluster solves that reached maxiter, summed over
+        the calls), max_iterations, max_residual (largest final | |r|^2 - d^2 | / d^2) and calls"""
+        if self._cons is None:
+            raise RuntimeError("VerletRun.constraint_stats: no constraints are set")
+        return self._stats_record(self._chk_dev[1:].cpu())
 
     def _pack_and_send_ghosts(self):
         """forward exchange on the current stream: x[nlocal:] <- the owners' positions (+ image shifts)"""
@@ -630,5 +795,5 @@ class VerletRun:
         return w.cpu().numpy().reshape(3, 3)
 
     def temperature(self, natoms_all: int) -> float:
-        """LAMMPS compute temp: 2 KE / ((3 N - 3) k_B)"""
-        return 2.0 * self.kinetic_energy() / ((3.0 * natoms_all - 3.0) * BOLTZ)
+        """LAMMPS compute temp: 2 KE / ((3 N - 3 - nb) k_B), nb the constrained bonds (set_constraints; 0 without)"""
+        return 2.0 * self.kinetic_energy() / ((3.0 * natoms_all - 3.0 - self._ncons) * BOLTZ)
