@@ -242,12 +242,14 @@ class DomainComm:
         if all(self.periodic):
             x = x - torch.floor((x - lo) / L) * L
             x = torch.where(x >= lo + L, lo.expand_as(x), x)   # a coordinate that rounds up onto the upper face
+            x = torch.where(x < lo, lo.expand_as(x), x)        # a quotient that rounds up to the integer (wrap_kernel has the same line)
         else:
             x = x.clone()
             for d in range(3):
                 if self.periodic[d]:
                     x[:, d] -= torch.floor((x[:, d] - lo[d]) / L[d]) * L[d]
                     x[:, d] = torch.where(x[:, d] >= lo[d] + L[d], lo[d], x[:, d])
+                    x[:, d] = torch.where(x[:, d] < lo[d], lo[d], x[:, d])
         if not self.multi:
             return (x,) + tuple(per_atom)
         P = torch.tensor(self.grid, dtype=torch.float64, device=x.device)

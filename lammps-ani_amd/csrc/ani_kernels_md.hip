@@ -180,6 +180,7 @@ __global__ __launch_bounds__(256) void wrap_kernel(double* __restrict__ x, int n
   double v = x[t];
   v -= floor((v - lo) / L) * L;
   if (v >= lo + L) v = lo;   // a coordinate that rounds up onto the upper face
+  if (v < lo) v = lo;        // a quotient that rounds up to the integer: the image a hair under the upper face comes out a hair under lo
   x[t] = v;
 }
 
