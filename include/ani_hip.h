@@ -303,6 +303,56 @@ int ani_find_molecules(ani_handle* h, int ntotal, int nlocal, const double* coor
 const char* ani_species_symbol(const ani_handle* h, int s);
 
 /*
+ * Radial distribution functions: histograms of pair distances per ordered species pair, accumulated on the device over any number
+ * of frames, from the list the step already keeps (the reference's runs leave this to LAMMPS: `compute rdf` with `fix ave/time`).
+ * Works on the list installed in the handle for this epoch (an ago == 0 call or ani_build_list*; dense segments or capacity rows).
+ * The installed list holds every entry the caller's list or the builder's cutneigh gave it -- nothing is dropped by distance, the
+ * screening to the AEV cutoffs happens per step in a buffer of its own -- so it is complete to rmax whenever it is complete to the
+ * radial cutoff Rcr, which is what a step needs of it anyway.  Arms nothing, does not touch the step's state, may be called between
+ * any two steps, any number of times per epoch.  The results are integers: exact, and independent of scheduling.
+ *
+ * ani_rdf_configure   host call at set-up time: allocates and zeroes the accumulators for npair histograms of nbins bins on
+ *     [0, rmax).  pairs[npair][2]: species indices (a, b) of the model (ani_species_symbol names them); (a, b) and (b, a) are
+ *     different pairs and both may be listed.  ANI_ERR_ARG, with a message that names the offender, when nbins < 1 or nbins > 4096;
+ *     rmax is not a positive finite number; rmax is above the model's radial cutoff ani_cutoff_radial(h) (the list is only
+ *     guaranteed complete inside the force cutoff); a species index lies outside [0, ani_num_species(h)); the same ordered pair is
+ *     listed twice; the handle is a half-list handle (use_fullnbr == 0).  A refused call changes nothing.  npair == 0 or
+ *     pairs == NULL clears the configuration.  Reconfiguring discards what was accumulated.  Synchronises the device.
+ * ani_rdf_accumulate_device   one frame.  Every pointer is device memory on the handle's device, nothing synchronises, stream == NULL
+ *     is the HIP default stream.  ANI_ERR_ARG when nothing is configured, no list is installed, ntotal / nlocal differ from the
+ *     epoch's, d_x is NULL, or the handle is a half-list handle; a refused call accumulates nothing.  nlocal == 0 is a valid frame
+ *     that adds no counts.
+ * ani_rdf_accumulate   the same with host positions: uploads them, runs the device entry on the handle's stream and synchronises.
+ * ani_rdf_read   waits for all work on the device (the device entry runs on the caller's streams), then copies the accumulators
+ *     out: counts[npair][nbins], centres[npair], frames[1], all uint64; any pointer may be NULL, nothing is written past these
+ *     sizes.  reset != 0 zeroes counts, centres and frames after the copy and keeps the configuration.  ANI_ERR_ARG when nothing is
+ *     configured.
+ *
+ * Definitions.  x: the doubles passed in (d_x / coordinates [ntotal*3]), NOT the handle's packed fp32 positions; the handle's
+ * precision does not matter.  s: the species the handle keeps for the owned and ghost atoms of the epoch.
+ *   Centre    ii in [0, nlocal) with i = ilist[ii] in [0, nlocal): an owned atom.  Ghosts are never centres, so with several ranks
+ *             every ordered pair (owned centre, neighbour) is counted by exactly one rank and the ranks' words add up.
+ *   Count     an entry j of centre i's list segment with j in [0, ntotal) (others are skipped), pair p = (s_i, s_j) configured,
+ *             r = sqrt(dx*dx + dy*dy + dz*dz) in fp64 with d = x_j - x_i, and r < rmax.  A ghost neighbour counts like any other;
+ *             an atom's own periodic image is a legitimate neighbour.  The list decides what is a pair: an entry listed twice
+ *             counts twice, a pair the list does not hold is not counted.
+ *   Bin       k = (int)(r * inv_dr), truncation of the fp64 product, with inv_dr = (double)nbins / rmax computed once; the entry
+ *             adds 1 to counts[p][k] when k < nbins (r * inv_dr can round up to nbins just below rmax: such an entry is dropped).
+ *             Bin k covers [k * rmax / nbins, (k + 1) * rmax / nbins).
+ *   Centres   centres[p] grows per frame by the number of centres with s_i == a_p, whether or not they have neighbours.
+ *   Frame     every accepted ani_rdf_accumulate* call adds 1 to frames.
+ * One launch per frame (lammps-ani_amd/csrc/ani_kernels_rdf.hip): sixteen lanes per centre, a workgroup-private histogram of
+ * 32-bit counters in 32 KiB of static LDS flushed once per workgroup into the 64-bit words with integer atomics; above
+ * 8192 bins in all (npair * nbins) the kernel counts straight into the 64-bit words.  Integer atomics only; no lane, wave or
+ * workgroup waits for another.  Options "rdf_lanes" (16, default, or 64: a wave per centre) and "rdf_lds" (default 1; 0 counts
+ * straight into global memory at any size) exist for measurements; the results do not depend on them.
+ */
+int ani_rdf_configure(ani_handle* h, int nbins, double rmax, const int* pairs /* [npair][2] species a, b */, int npair);
+int ani_rdf_accumulate_device(ani_handle* h, int ntotal, int nlocal, const double* d_x, void* stream);
+int ani_rdf_accumulate(ani_handle* h, int ntotal, int nlocal, const double* coordinates);
+int ani_rdf_read(ani_handle* h, uint64_t* counts /* [npair][nbins] */, uint64_t* centres /* [npair] */, uint64_t* frames, int reset);
+
+/*
  * Ghost forces over RCCL instead of the caller's host MPI (the reference: comm->reverse_comm(this) after the D2H copy,
  * src/pair_ani.cpp:197-201,461-484).  With a communicator of include/ani_comm.h attached (maps of the epoch installed by the
  * caller: ani_comm_set_epoch, and ani_comm_set_ghost_order when the ghost block is in LAMMPS' swap order), the host-pointer

@@ -24,7 +24,8 @@ EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
            "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
            "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts",
-           "ani_set_bond_table", "ani_find_molecules_device", "ani_find_molecules", "ani_species_symbol"]
+           "ani_set_bond_table", "ani_find_molecules_device", "ani_find_molecules", "ani_species_symbol",
+           "ani_rdf_configure", "ani_rdf_accumulate_device", "ani_rdf_accumulate", "ani_rdf_read"]
 # include/ani_comm.h: the device-side ghost exchange over RCCL
 COMM_EXPORTS = ["ani_comm_get_unique_id", "ani_comm_create", "ani_comm_create_local", "ani_comm_destroy", "ani_comm_last_error", "ani_comm_rank",
                 "ani_comm_size", "ani_comm_plan", "ani_comm_exchange_counts", "ani_comm_alltoallv", "ani_comm_set_epoch",
@@ -138,6 +139,10 @@ def lib():
                                          C.c_void_p]
         L.ani_species_symbol.argtypes = [C.c_void_p, C.c_int]
         L.ani_species_symbol.restype = C.c_char_p
+        L.ani_rdf_configure.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int]
+        L.ani_rdf_accumulate_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_rdf_accumulate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.ani_rdf_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.ani_host_register.argtypes = [C.c_void_p, C.c_size_t]
         L.ani_host_unregister.argtypes = [C.c_void_p]
         L.ani_last_mlp_kernel.restype = C.c_char_p
@@ -219,6 +224,33 @@ def formula_dict(rows, symbols) -> dict:
         k = formula_string(row[:-1], symbols)
         out[k] = out.get(k, 0) + int(row[-1])
     return out
+
+
+def rdf_normalise(counts, centres, nbins, rmax, pairs, n_of_species, volume) -> dict:
+    """The accumulators of ani_rdf_read as radial distribution functions, normalised like LAMMPS ``compute rdf``.  Pure numpy.
+    counts [npair, nbins] and centres [npair] (any frames summed), pairs [npair, 2] species indices (a, b), n_of_species[s] the
+    number of atoms of species s in the box, volume in A^3.  Returns a dict:
+      r      [nbins]         bin centres
+      g      [npair, nbins]  counts[p, k] / (centres[p] * rho_b * 4 pi / 3 * (r_hi^3 - r_lo^3)), rho_b = (N_b - delta_ab) / volume
+      coord  [npair, nbins]  cumsum(counts[p]) / centres[p]: the running coordination number
+    A pair with centres[p] == 0 or rho_b == 0 gives zeros, not NaN."""
+    nbins = int(nbins)
+    counts = np.asarray(counts, dtype=np.float64).reshape(-1, nbins)
+    centres = np.asarray(centres, dtype=np.float64).reshape(-1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n_of = np.asarray(n_of_species, dtype=np.float64)
+    assert counts.shape[0] == centres.shape[0] == pairs.shape[0]
+    edges = np.arange(nbins + 1, dtype=np.float64) * (float(rmax) / nbins)
+    shell = 4.0 * np.pi / 3.0 * (edges[1:] ** 3 - edges[:-1] ** 3)
+    g, coord = np.zeros_like(counts), np.zeros_like(counts)
+    for p, (a, b) in enumerate(pairs.tolist()):
+        if centres[p] == 0:
+            continue
+        coord[p] = np.cumsum(counts[p]) / centres[p]
+        rho_b = (n_of[b] - (1.0 if a == b else 0.0)) / float(volume)
+        if rho_b > 0:
+            g[p] = counts[p] / (centres[p] * rho_b * shell)
+    return dict(r=0.5 * (edges[1:] + edges[:-1]), g=g, coord=coord)
 
 
 class ANI:
@@ -478,6 +510,61 @@ class ANI:
         [formula_cap, S + 1] (rows in unspecified order), d_summary int64 [6]."""
         self._check(self._lib.ani_find_molecules_device(self._h, int(ntotal), int(nlocal), d_x, d_owner, d_mol_of_atom, d_formula,
                                                         int(formula_cap), d_summary, stream))
+
+    def rdf_configure(self, nbins: int, rmax: float, pairs):
+        """ani_rdf_configure: npair histograms of nbins bins on [0, rmax) A.  pairs: ordered (centre, neighbour) species pairs as
+        indices or symbols, [("O", "O"), ("O", "H"), ...]; None or an empty list clears the configuration.  Reconfiguring discards
+        what was accumulated."""
+        if pairs is None or len(pairs) == 0:
+            self._check(self._lib.ani_rdf_configure(self._h, int(nbins), float(rmax), None, 0))
+            self._rdf = None
+            return
+        sym = None
+        idx = []
+        for pr in pairs:
+            a, b = pr
+            for v in (a, b):
+                if isinstance(v, str):
+                    sym = sym or self.species_symbols()
+                    if v not in sym:
+                        raise AniError(f"rdf_configure: the model has no species {v!r} (it has {sym})")
+                    v = sym.index(v)
+                idx.append(int(v))
+        p = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, 2)
+        self._check(self._lib.ani_rdf_configure(self._h, int(nbins), float(rmax), p.ctypes.data, int(p.shape[0])))
+        self._rdf = (int(nbins), float(rmax), p)
+
+    def rdf_config(self):
+        """(nbins, rmax, pairs int32 [npair, 2]) of the last accepted rdf_configure, None when nothing is configured"""
+        return getattr(self, "_rdf", None)
+
+    def rdf_accumulate(self, inp_or_x, nlocal=None):
+        """ani_rdf_accumulate: one frame on the installed list.  inp_or_x: a harness.RankInput (its positions), or an [ntotal, 3]
+        array with ``nlocal`` (default: all of it)."""
+        if hasattr(inp_or_x, "nlocal"):
+            x, nl = inp_or_x.x, inp_or_x.nlocal
+        else:
+            x = inp_or_x
+            nl = len(x) if nlocal is None else int(nlocal)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        self._check(self._lib.ani_rdf_accumulate(self._h, int(x.shape[0]), int(nl), x.ctypes.data))
+
+    def rdf_accumulate_device(self, ntotal, nlocal, d_x, stream=None):
+        """ani_rdf_accumulate_device: d_x is the device address of float64 [ntotal, 3]; nothing synchronises"""
+        self._check(self._lib.ani_rdf_accumulate_device(self._h, int(ntotal), int(nlocal), d_x, stream))
+
+    def rdf_read(self, reset: bool = False):
+        """ani_rdf_read: (counts uint64 [npair, nbins], centres uint64 [npair], frames int); reset zeroes the accumulators after
+        the copy and keeps the configuration"""
+        cfg = self.rdf_config()
+        if cfg is None:
+            raise AniError("rdf_read: nothing is configured (rdf_configure)")
+        nbins, _, p = cfg
+        counts = np.zeros((p.shape[0], nbins), dtype=np.uint64)
+        centres = np.zeros(p.shape[0], dtype=np.uint64)
+        frames = np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.ani_rdf_read(self._h, counts.ctypes.data, centres.ctypes.data, frames.ctypes.data, int(bool(reset))))
+        return counts, centres, int(frames[0])
 
     def last_mlp_kernel(self) -> str:
         return self._lib.ani_last_mlp_kernel(self._h).decode()

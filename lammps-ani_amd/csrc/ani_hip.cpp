@@ -201,6 +201,12 @@ struct ani_handle {
   DevBuf<unsigned long long> mol_words;   // counters | keys
   DevBuf<long long> mol_owner, mol_summary;
   DevBuf<int> mol_out;                    // mol_of_atom | formula rows
+  // radial distribution functions (ani_rdf_*): the configuration and the accumulators (ani_kernels_rdf.hip: RdfArgs)
+  int rdf_npair = 0, rdf_nbins = 0;       // npair == 0: nothing configured
+  double rdf_rmax = 0.0;
+  int rdf_lanes = 16, rdf_lds = 1;        // ani_set_option("rdf_lanes" / "rdf_lds")
+  DevBuf<int> rdf_ints;                   // slot_of [S][S] | pair_a [npair]
+  DevBuf<unsigned long long> rdf_words;   // hist [npair][nbins] | centres [npair] | frames
   int nlocal = 0, ntotal = 0, nrows = 0;
   long long npairs = 0;
   int count[kMaxSpecies] = {0}, row_start[kMaxSpecies] = {0};
@@ -1695,6 +1701,7 @@ void ani_destroy(ani_handle* h) {
   h->gaev_parts64.release(); h->dv_fbuf.release(); h->dv_fbuf64.release(); h->dv_tmp.release(); h->dv_stage.release();
   h->dv_part.release(); h->dv_ticket.release();
   h->bond_cut2.release(); h->mol_ints.release(); h->mol_words.release(); h->mol_owner.release(); h->mol_summary.release(); h->mol_out.release();
+  h->rdf_ints.release(); h->rdf_words.release();
   h->virial_acc.release(); h->aev.release(); h->gaev.release(); h->act.release(); h->aev64.release(); h->gaev64.release(); h->act64.release(); h->e_rows64.release(); h->fbuf64.release(); h->e_rows.release(); h->fbuf.release();
   for (int fi = 0; fi < 4; fi++) free_fused(h, fi);
   h->fused_counter.release(); h->gaev_parts.release(); h->fused_sched.release();
@@ -2519,6 +2526,124 @@ int ani_find_molecules(ani_handle* h, int ntotal, int nlocal, const double* coor
   return ANI_OK;
 }
 
+// ---- radial distribution functions (ani_rdf_*): see include/ani_hip.h -------------------------------------------------------
+int ani_rdf_configure(ani_handle* h, int nbins, double rmax, const int* pairs, int npair) {
+  if (!h) return ANI_ERR_ARG;
+  if (!h->use_fullnbr) { h->err = "ani_rdf_configure: the handle was created for half lists (use_fullnbr = 0)"; return ANI_ERR_ARG; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (!pairs || npair == 0) {   // cleared
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->rdf_npair = 0;
+    return ANI_OK;
+  }
+  const int S = h->model.S;
+  if (npair < 0) { h->err = "ani_rdf_configure: npair = " + std::to_string(npair) + " is negative"; return ANI_ERR_ARG; }
+  if (nbins < 1 || nbins > kRdfMaxBins) {
+    h->err = "ani_rdf_configure: nbins = " + std::to_string(nbins) + " is outside [1, " + std::to_string(kRdfMaxBins) + "]";
+    return ANI_ERR_ARG;
+  }
+  if (!(rmax > 0.0) || !std::isfinite(rmax)) { h->err = "ani_rdf_configure: rmax = " + std::to_string(rmax) + " is not a positive finite number"; return ANI_ERR_ARG; }
+  if (rmax > h->model.Rcr) {
+    h->err = "ani_rdf_configure: rmax = " + std::to_string(rmax) + " A is above the radial cutoff " + std::to_string(h->model.Rcr) +
+             " A (the list is only complete inside the force cutoff)";
+    return ANI_ERR_ARG;
+  }
+  std::vector<int> tab((size_t)S * S + (size_t)npair, -1);
+  for (int p = 0; p < npair; p++) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    for (int v : {a, b})
+      if (v < 0 || v >= S) {
+        h->err = "ani_rdf_configure: pair " + std::to_string(p) + " names species " + std::to_string(v) + ", outside [0, " + std::to_string(S) + ")";
+        return ANI_ERR_ARG;
+      }
+    if (tab[(size_t)a * S + b] >= 0) {
+      h->err = "ani_rdf_configure: the ordered pair (" + h->model.symbols[a] + ", " + h->model.symbols[b] + ") is listed twice (pairs " +
+               std::to_string(tab[(size_t)a * S + b]) + " and " + std::to_string(p) + ")";
+      return ANI_ERR_ARG;
+    }
+    tab[(size_t)a * S + b] = p;
+    tab[(size_t)S * S + p] = a;
+  }
+  // accumulations still in flight write the words that are replaced here (rare: set-up time)
+  HIP_TRY(h, hipDeviceSynchronize());
+  h->rdf_npair = 0;   // a failure below leaves nothing configured
+  const size_t words = (size_t)npair * nbins + (size_t)npair + 1;
+  HIP_TRY(h, h->rdf_ints.reserve(tab.size()));
+  HIP_TRY(h, h->rdf_words.reserve(words));
+  HIP_TRY(h, hipMemcpy(h->rdf_ints.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemset(h->rdf_words.p, 0, sizeof(unsigned long long) * words));
+  HIP_TRY(h, hipStreamSynchronize(nullptr));   // the handle's streams do not wait for the null stream
+  h->rdf_npair = npair; h->rdf_nbins = nbins; h->rdf_rmax = rmax;
+  return ANI_OK;
+}
+
+static int rdf_accumulate_args(ani_handle* h, int ntotal, int nlocal) {
+  if (!h) return ANI_ERR_ARG;
+  if (!h->use_fullnbr) { h->err = "ani_rdf_accumulate: the handle was created for half lists (use_fullnbr = 0)"; return ANI_ERR_ARG; }
+  if (h->rdf_npair == 0) { h->err = "ani_rdf_accumulate: nothing is configured (ani_rdf_configure)"; return ANI_ERR_ARG; }
+  if (!h->have_list) { h->err = "ani_rdf_accumulate: no neighbour list is installed (a call with ago == 0, or ani_build_list*)"; return ANI_ERR_ARG; }
+  if (ntotal != h->ntotal || nlocal != h->nlocal) {
+    h->err = "ani_rdf_accumulate: ntotal / nlocal = " + std::to_string(ntotal) + " / " + std::to_string(nlocal) +
+             " differ from the installed list's " + std::to_string(h->ntotal) + " / " + std::to_string(h->nlocal);
+    return ANI_ERR_ARG;
+  }
+  return ANI_OK;
+}
+
+int ani_rdf_accumulate_device(ani_handle* h, int ntotal, int nlocal, const double* d_x, void* stream) {
+  const int rc = rdf_accumulate_args(h, ntotal, nlocal);
+  if (rc) return rc;
+  if (!d_x) { h->err = "ani_rdf_accumulate: null positions"; return ANI_ERR_ARG; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const int S = h->model.S;
+  RdfArgs a{};
+  a.nlocal = nlocal; a.ntotal = ntotal; a.S = S;
+  a.ilist = h->ilist.p; a.nbr_off = h->nbr_off.p; a.numneigh = h->numneigh.p; a.jlist = h->jlist.p; a.species = h->species.p;
+  a.x = d_x;
+  a.slot_of = h->rdf_ints.p; a.pair_a = h->rdf_ints.p + (size_t)S * S;
+  a.npair = h->rdf_npair; a.nbins = h->rdf_nbins;
+  a.rmax = h->rdf_rmax; a.inv_dr = (double)h->rdf_nbins / h->rdf_rmax;
+  a.hist = h->rdf_words.p; a.centres = a.hist + (size_t)a.npair * a.nbins; a.frames = a.centres + a.npair;
+  TraceRange tr("ani: rdf sample");
+  launch_rdf_accumulate(a, h->rdf_lanes, h->rdf_lds, (hipStream_t)stream);
+  HIP_TRY(h, take_launch_error());
+  return ANI_OK;
+}
+
+int ani_rdf_accumulate(ani_handle* h, int ntotal, int nlocal, const double* coordinates) {
+  int rc = rdf_accumulate_args(h, ntotal, nlocal);
+  if (rc) return rc;
+  if (!coordinates) { h->err = "ani_rdf_accumulate: null positions"; return ANI_ERR_ARG; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  HIP_TRY(h, h->x64.reserve((size_t)std::max(ntotal, 1) * 3));
+  h->x64_from = nullptr;   // the staging array no longer holds what ani_build_list uploaded
+  HIP_TRY(h, hipMemcpyAsync(h->x64.p, coordinates, sizeof(double) * 3 * (size_t)ntotal, hipMemcpyHostToDevice, st));
+  rc = ani_rdf_accumulate_device(h, ntotal, nlocal, h->x64.p, st);
+  if (rc) return rc;
+  HIP_TRY(h, hipStreamSynchronize(st));
+  return ANI_OK;
+}
+
+int ani_rdf_read(ani_handle* h, uint64_t* counts, uint64_t* centres, uint64_t* frames, int reset) {
+  if (!h) return ANI_ERR_ARG;
+  if (h->rdf_npair == 0) { h->err = "ani_rdf_read: nothing is configured (ani_rdf_configure)"; return ANI_ERR_ARG; }
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the accumulators are 64-bit words");
+  HIP_TRY(h, hipSetDevice(h->device));
+  // the device entry runs on the caller's streams: everything that writes the accumulators is waited for
+  HIP_TRY(h, hipDeviceSynchronize());
+  const size_t nh = (size_t)h->rdf_npair * h->rdf_nbins, np = (size_t)h->rdf_npair;
+  const unsigned long long* w = h->rdf_words.p;
+  if (counts) HIP_TRY(h, hipMemcpy(counts, w, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
+  if (centres) HIP_TRY(h, hipMemcpy(centres, w + nh, sizeof(uint64_t) * np, hipMemcpyDeviceToHost));
+  if (frames) HIP_TRY(h, hipMemcpy(frames, w + nh + np, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (reset) {
+    HIP_TRY(h, hipMemset(h->rdf_words.p, 0, sizeof(unsigned long long) * (nh + np + 1)));
+    HIP_TRY(h, hipStreamSynchronize(nullptr));
+  }
+  return ANI_OK;
+}
+
 int ani_debug_list(ani_handle* h, const int** d_numneigh, const int** d_nbr_off, const int** d_jlist) {
   if (!h || !h->have_list) return ANI_ERR_ARG;
   if (d_numneigh) *d_numneigh = h->numneigh.p;
@@ -2539,6 +2664,15 @@ int ani_set_option(ani_handle* h, const char* name, int value) {
     h->prune = value != 0;
     h->have_list = false;  // takes effect at the next rebuild (ago = 0), which the caller must issue
     h->active_mask = -1;
+    return ANI_OK;
+  }
+  if (strcmp(name, "rdf_lanes") == 0) {
+    if (value != 16 && value != 64) { h->err = "ani_set_option: rdf_lanes is 16 or 64"; return ANI_ERR_ARG; }
+    h->rdf_lanes = value;
+    return ANI_OK;
+  }
+  if (strcmp(name, "rdf_lds") == 0) {
+    h->rdf_lds = value != 0;
     return ANI_OK;
   }
   if (strcmp(name, "mlp_chain") == 0) {

@@ -412,6 +412,33 @@ struct MolArgs {
 // six launches on st, nothing waits: see ani_kernels_mol.hip
 void launch_find_molecules(const MolArgs& a, hipStream_t st);
 
+// ---- radial distribution functions (ani_kernels_rdf.hip; ani_rdf_*, include/ani_hip.h) -----------------------------------
+// A workgroup's private histogram: 32-bit counters in static LDS (32 KiB).  npair * nbins above it: the kernel counts straight
+// into the global words with the same integer atomics.
+constexpr int kRdfLdsBins = 8192;
+constexpr int kRdfMaxBins = 4096;   // ani_rdf_configure: nbins per pair
+constexpr int kRdfMaxBlocks = 1024; // workgroups of a launch (grid-stride over the centres): one flush per workgroup
+struct RdfArgs {
+  int nlocal, ntotal, S;
+  // the installed list, as MolArgs takes it
+  const int* ilist;
+  const int* nbr_off;
+  const int* numneigh;
+  const int* jlist;
+  const int* species;        // [ntotal]
+  const double* x;           // [ntotal][3] the caller's positions
+  const int* slot_of;        // [S][S] histogram of the ordered species pair (centre, neighbour), -1: not asked for
+  const int* pair_a;         // [npair] centre species of every histogram
+  int npair, nbins;
+  double rmax, inv_dr;       // inv_dr = nbins / rmax
+  unsigned long long* hist;     // [npair][nbins]
+  unsigned long long* centres;  // [npair]
+  unsigned long long* frames;   // [1]
+};
+// one launch on st, nothing waits.  lanes: 16 or 64 lanes per centre; use_lds: 0 forces the global-atomics path (measurements),
+// otherwise the LDS histogram is used whenever npair * nbins <= kRdfLdsBins
+void launch_rdf_accumulate(const RdfArgs& a, int lanes, int use_lds, hipStream_t st);
+
 // ---- double precision path (ani_kernels_f64.hip) ------------------------------------------------------------
 struct Aev64Params {
   int S, nR, nA, nZ, radial_len, aev_len, aev_stride, compat;

@@ -153,6 +153,7 @@ class VerletRun:
         self._cap = 0
         self._cons = None      # bond constraints (set_constraints): None, or the device tables and parameters of the two stages
         self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
+        self._rdf_every = 0    # radial distribution functions (set_rdf): 0 = none, else a frame every so many steps
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
             self._comm_stream = torch.cuda.current_stream(device) if os.environ.get("ANI_MD_OVERLAP_ONE_STREAM") else \
@@ -423,6 +424,9 @@ class VerletRun:
                                        "capacity (ANI_ERR_CAPACITY) or the forces diverged")
                 rebuild = worst > (0.5 * self.skin) ** 2
         self._ghosts_and_forces(rebuild)
+        # on every path above the ghost rows of x are now the images of this step's owned positions
+        if self._rdf_every and self.step_no % self._rdf_every == 0:
+            self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
 
     def _ghosts_and_forces(self, rebuild: bool):
         """re-neighbouring or forward ghost positions, then forces and reverse ghost forces, by whichever path the loop is on"""
@@ -771,6 +775,57 @@ class VerletRun:
         if summ[1] > formula_cap:
             raise AniError(f"find_molecules: {int(summ[1])} distinct compositions, formula_cap is {formula_cap}")
         return mol[:n].cpu().numpy(), formula_dict(rows[: int(summ[1])].cpu().numpy(), self.ani.species_symbols()), summ
+
+    def set_rdf(self, pairs, nbins: int = 100, rmax=None, every: int = 1):
+        """``compute rdf`` + ``fix ave/time``: radial distribution functions accumulated on the device (ani_rdf_*,
+        include/ani_hip.h).  pairs: ordered (centre, neighbour) species pairs as symbols or indices, [("O", "O"), ("O", "H"), ...];
+        nbins bins on [0, rmax), rmax None = the loop's force cutoff (cutneigh - skin; never above the model's radial cutoff).
+        From here on every step with step_no % every == 0 adds one frame right after its force evaluation: one launch on the
+        loop's stream with the loop's own positions, no host synchronisation.  minimize() does not sample.  An empty `pairs`
+        clears the RDF: the loop launches what it launched before.  Calling it again discards what was accumulated.  One rank
+        only: the per-rank counts are summable, the sum over ranks is not built."""
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.set_rdf: one rank only (the ranks' counts are not summed)")
+        if pairs is None or len(pairs) == 0:
+            self._rdf_every = 0
+            self.ani.rdf_configure(1, 1.0, None)
+            return
+        if int(every) < 1:
+            raise ValueError("VerletRun.set_rdf: every >= 1")
+        # a refused configuration raises here and changes nothing: what was set before goes on
+        self.ani.rdf_configure(int(nbins), self.cutneigh - self.skin if rmax is None else float(rmax), pairs)
+        self._rdf_every = int(every)
+
+    def _refresh_ghosts(self):
+        """the ghost rows of x as images of the owned atoms' positions of this moment (a step's first kernel does the same)"""
+        n, ng = self.nlocal, self.ntotal - self.nlocal
+        if ng and self._fused:
+            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), self.dc.send_idx.data_ptr(), self.dc.send_shift.data_ptr(),
+                                                       n, ng, self._stream))
+        elif ng:
+            self.dc.forward_positions(self.x)
+
+    def sample_rdf(self):
+        """one frame now, on the current positions (whatever `every` says)"""
+        if self.ani.rdf_config() is None:
+            raise RuntimeError("VerletRun.sample_rdf: no RDF is set (set_rdf)")
+        self._refresh_ghosts()
+        self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
+
+    def rdf(self, reset: bool = False) -> dict:
+        """Read and normalise what was accumulated (ani_hip.rdf_normalise: r, g, coord), plus the raw counts [npair, nbins],
+        centres [npair], frames, and pairs [npair, 2].  Species counts from the owned atoms, the volume from the box.  reset:
+        zero the accumulators afterwards."""
+        from .ani_hip import rdf_normalise
+        cfg = self.ani.rdf_config()
+        if cfg is None:
+            raise RuntimeError("VerletRun.rdf: no RDF is set (set_rdf)")
+        nbins, rmax, pairs = cfg
+        counts, centres, frames = self.ani.rdf_read(reset=reset)
+        n_of = np.bincount(self.species[: self.nlocal].cpu().numpy(), minlength=len(self.ani.species_symbols()))
+        out = rdf_normalise(counts, centres, nbins, rmax, pairs, n_of, float(np.prod(self._box_len_np)))
+        out.update(counts=counts, centres=centres, frames=frames, pairs=pairs.copy())
+        return out
 
     # ---- thermo ------------------------------------------------------------------------------------------
     def kinetic_energy(self) -> float:
