@@ -175,6 +175,75 @@ int ani_md_shake_positions(double* x, double* v, const int* cl, const double* d,
 int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const double* d, int nc, const double* w,
                              const double* len3, int periodic_mask, void* stream);
 
+/*
+ * Nose-Hoover chain at constant volume (LAMMPS `fix nvt`, the `temp` half of `fix npt`: Martyna, Klein, Tuckerman, J. Chem. Phys. 97
+ * (1992) 2635; the explicit integrator of Martyna, Tuckerman, Tobias, Klein, Mol. Phys. 87 (1996) 1117) and the thermo record of
+ * `thermo_style custom pe ke etotal temp press`.  fp64 whatever the handle.  One rank.  No floating-point atomics: every sum is
+ * per-block partials (256 threads, xor butterflies inside a wave, the four waves in order), then one workgroup that strides over the
+ * partials and sums its 256 accumulators in the same fixed order -- the same inputs give bitwise the same record.
+ *
+ * Constants: k_B = 0.0019872067 kcal/mol/K, mvv2e = 48.88821291^2, nktv2p = 68568.415 (atm).
+ *
+ * Chain half-step, from K2 = sum_i m_i |v_i|^2 mvv2e (twice the kinetic energy), t_target, tdof and the parameters:
+ *   kt = k_B t_target, ket = tdof kt, tf = 1 / t_period, Q[0] = ket / tf^2, Q[k >= 1] = kt / tf^2 (from t_target, at every call),
+ *   nf = 1 / nc_tchain, dfac = 1 - dt drag / nc_tchain, M = mtchain <= ANI_MD_NH_MAXCHAIN, eta_dot[M] read as 0.
+ *     eta_dotdot[0] = (K2 - ket) / Q[0];  s = 1
+ *     repeat nc_tchain times:
+ *       for k = M-1 .. 1:  e = exp(-nf dt/8 eta_dot[k+1]);  eta_dot[k] = ((eta_dot[k] e + eta_dotdot[k] nf dt/4) dfac) e
+ *       e = exp(-nf dt/8 eta_dot[1]);  eta_dot[0] = ((eta_dot[0] e + eta_dotdot[0] nf dt/4) dfac) e
+ *       fac = exp(-nf dt/2 eta_dot[0]);  s *= fac;  K2 *= fac fac;  eta_dotdot[0] = (K2 - ket) / Q[0]
+ *       eta[k] += nf dt/2 eta_dot[k]  for all k
+ *       eta_dot[0] = (eta_dot[0] e + eta_dotdot[0] nf dt/4) e                                            (the same e)
+ *       for k = 1 .. M-1:  e = exp(-nf dt/8 eta_dot[k+1]);  eta_dot[k] *= e;
+ *                          eta_dotdot[k] = (Q[k-1] eta_dot[k-1]^2 - kt) / Q[k];  eta_dot[k] = (eta_dot[k] + eta_dotdot[k] nf dt/4) e
+ *     ecouple = ket eta[0] + Q[0] eta_dot[0]^2 / 2 + sum_{k >= 1} (kt eta[k] + Q[k] eta_dot[k]^2 / 2)
+ *   The caller multiplies every velocity by s.  eta_dotdot is state: the first loop of a call uses the upper links' accelerations
+ *   that the call before left.
+ *
+ * State: ANI_MD_NH_NSTATE doubles on the device:
+ *   [0] half-steps done   [1] K2 after the scaling   [2] s of the last half-step   [3] its t_target   [4] ecouple   [5] tdof
+ *   [6] calls that found K2 non-finite   [7] 0   [8..16) eta   [16..24) eta_dot   [24..32) eta_dotdot   (unused links stay 0)
+ *   A call that finds K2 non-finite writes s = 1 (and [1] = that K2, [3], [5]), adds one to [6] and leaves [0], [4] and the chain.
+ *
+ * ani_md_nh_work_size   doubles of scratch for nlocal atoms: one partial per block of 256 atoms (host function, no device).
+ * ani_md_nh_init        zeroes the record.
+ * ani_md_nh_kinetic     work[b] = K2 of the owned atoms of block b (b < ceil(nlocal / 256)); mass[nlocal] in g/mol.
+ * ani_md_nh_chain       one workgroup.  npart > 0: K2 = work[0] + .. + work[npart - 1] in the fixed order;  npart == 0: K2 = state[1].
+ *                       Then the half-step above, and the whole record is written.  params is a host pointer.
+ * ani_md_nh_scale       v *= state[2].
+ * ani_md_nh_initial_integrate   v = state[2] v first, then ani_md_initial_integrate.
+ * ani_md_nh_final_integrate     ani_md_final_integrate without Langevin (f is not written), and in the same pass the partials of
+ *                       ani_md_nh_kinetic on the new velocities into work: bit for bit what that call would write.
+ *
+ * ani_md_thermo: two launches (per-block partials of the six sums K_ab = sum_i m_i v_ia v_ib mvv2e in the order xx, yy, zz, xy, xz,
+ * yz, then one workgroup) into out[ANI_MD_THERMO_N], with W_ab = ev[1 + 3 a + b] the pair virial and V = volume:
+ *   [0] pe = ev[0]   [1] ke = (K_xx + K_yy + K_zz) / 2   [2] temp = 2 ke / (tdof k_B)
+ *   [3] press = (K_xx + K_yy + K_zz + W_xx + W_yy + W_zz) / (3 V) nktv2p
+ *   [4..10) P_ab = (K_ab + W_ab) / V nktv2p, xx yy zz xy xz yz   [10] etotal = pe + ke   [11] ecouple = nh_state[4] (0: NULL)
+ *   [12] econserve = etotal + ecouple   [13] volume   [14] K2 = 2 ke   [15] 0
+ *   with_virial == 0: [3..10) are NaN.  work: ani_md_thermo_work_size(nlocal) doubles.
+ */
+#define ANI_MD_NH_NSTATE 32
+#define ANI_MD_NH_MAXCHAIN 8
+#define ANI_MD_THERMO_N 16
+typedef struct ani_md_nh_params {
+  double dt, t_period, drag;
+  int mtchain, nc_tchain;
+} ani_md_nh_params;
+int ani_md_nh_work_size(int nlocal);
+int ani_md_nh_init(double* state, void* stream);
+int ani_md_nh_kinetic(const double* v, const double* mass, int nlocal, double* work, void* stream);
+int ani_md_nh_chain(double* state, const double* work, int npart, double t_target, double tdof, const ani_md_nh_params* params,
+                    void* stream);
+int ani_md_nh_scale(double* v, int nlocal, const double* state, void* stream);
+int ani_md_nh_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
+                                const double* x_built, double* d2max, const double* state, void* stream);
+int ani_md_nh_final_integrate(double* v, const double* f, const double* dtfm, const double* mass, int nlocal, double* work,
+                              void* stream);
+int ani_md_thermo_work_size(int nlocal);
+int ani_md_thermo(const double* v, const double* mass, int nlocal, const double* ev, int with_virial, double tdof, double volume,
+                  const double* nh_state, double* work, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

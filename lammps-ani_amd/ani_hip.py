@@ -56,6 +56,26 @@ FIRE_STOP_REASONS = ("running", "etol", "ftol", "maxiter", "non-finite")
 # ANI_MD_SHAKE_NSTATS words of include/ani_md.h (ani_md_shake_positions): the third is the bit pattern of a double
 SHAKE_NSTATS = 4
 SHAKE_STATS_KEYS = ("unconverged", "max_iterations", "max_residual", "calls")
+# the Nose-Hoover chain's state record and the thermo record of include/ani_md.h (ani_md_nh_*, ani_md_thermo)
+NH_NSTATE = 32
+NH_MAXCHAIN = 8
+NH_STATE_KEYS = ("half_steps", "k2", "s", "t_target", "ecouple", "tdof", "nonfinite")
+THERMO_N = 16
+THERMO_KEYS = ("pe", "ke", "temp", "press", "pxx", "pyy", "pzz", "pxy", "pxz", "pyz", "etotal", "ecouple", "econserve", "vol", "k2")
+
+
+class NhParams(C.Structure):
+    """ani_md_nh_params of include/ani_md.h"""
+    _fields_ = [("dt", C.c_double), ("t_period", C.c_double), ("drag", C.c_double), ("mtchain", C.c_int), ("nc_tchain", C.c_int)]
+
+
+def nh_state_dict(rec, mtchain: int = NH_MAXCHAIN) -> dict:
+    """the ANI_MD_NH_NSTATE doubles of a chain record (host array) as a dict; eta, eta_dot, eta_dotdot: the first mtchain links"""
+    rec = np.asarray(rec, dtype=np.float64)
+    out = dict(zip(NH_STATE_KEYS, rec[:7].tolist()))
+    for k, name in enumerate(("eta", "eta_dot", "eta_dotdot")):
+        out[name] = rec[8 + 8 * k: 8 + 8 * k + mtchain].copy()
+    return out
 
 
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
@@ -175,6 +195,17 @@ def lib():
                                              C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ani_md_rattle_velocities.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]
+        L.ani_md_nh_work_size.argtypes = [C.c_int]
+        L.ani_md_nh_init.argtypes = [C.c_void_p, C.c_void_p]
+        L.ani_md_nh_kinetic.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_md_nh_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(NhParams), C.c_void_p]
+        L.ani_md_nh_scale.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_md_nh_initial_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_nh_final_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_md_thermo_work_size.argtypes = [C.c_int]
+        L.ani_md_thermo.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

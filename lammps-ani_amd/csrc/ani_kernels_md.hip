@@ -668,6 +668,199 @@ __global__ __launch_bounds__(256) void rattle_velocities_kernel(const double* __
   }
 }
 
+// ---- Nose-Hoover chain and thermo record (include/ani_md.h, ani_md_nh_* / ani_md_thermo) ------------------------------------
+// Sums as FIRE's: per-block partials with block_sum_fixed, then one workgroup that strides over the partials and sums its 256
+// accumulators with block_sum_fixed again.  The chain itself is a few dozen flops on one thread.
+enum { NS_COUNT = 0, NS_K2, NS_S, NS_TTARGET, NS_ECOUPLE, NS_TDOF, NS_NONFINITE, NS_ZERO, NS_ETA = 8, NS_ETADOT = 16, NS_ETADOTDOT = 24,
+       NS_N = 32 };
+static_assert(NS_N == ANI_MD_NH_NSTATE && NS_ETADOT - NS_ETA == ANI_MD_NH_MAXCHAIN, "state layout of include/ani_md.h");
+constexpr double NH_BOLTZ = 0.0019872067, NH_MVV2E = 48.88821291 * 48.88821291, NH_NKTV2P = 68568.415;
+
+// m |v|^2 mvv2e of one atom, the multiply-adds spelled out: the same bits wherever it is inlined
+__device__ __forceinline__ double k2_term(double m, double v0, double v1, double v2) {
+  return (m * fma(v2, v2, fma(v1, v1, v0 * v0))) * NH_MVV2E;
+}
+
+__global__ __launch_bounds__(256) void nh_kinetic_kernel(const double* __restrict__ v, const double* __restrict__ mass, int n,
+                                                         double* __restrict__ part) {
+  __shared__ double red[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double k2 = 0.0;
+  if (i < n) k2 = k2_term(mass[i], v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2]);
+  k2 = block_sum_fixed(k2, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = k2;
+}
+
+__global__ __launch_bounds__(256) void nh_chain_kernel(double* __restrict__ state, const double* __restrict__ part, int npart,
+                                                       double t_target, double tdof, double kt, double ket,
+                                                       ani_md_nh_params p) {
+  __shared__ double red[4];
+  double K2 = 0.0;
+  for (int b = threadIdx.x; b < npart; b += 256) K2 += part[b];
+  K2 = block_sum_fixed(K2, red);
+  if (threadIdx.x != 0) return;
+  if (npart == 0) K2 = state[NS_K2];
+  state[NS_TTARGET] = t_target;
+  state[NS_TDOF] = tdof;
+  state[NS_ZERO] = 0.0;
+  if (!finite_d(K2)) {
+    state[NS_K2] = K2;
+    state[NS_S] = 1.0;
+    state[NS_NONFINITE] += 1.0;
+    return;
+  }
+  const int M = p.mtchain;
+  double eta[ANI_MD_NH_MAXCHAIN], ed[ANI_MD_NH_MAXCHAIN + 1], edd[ANI_MD_NH_MAXCHAIN], Q[ANI_MD_NH_MAXCHAIN];
+  // kt = k_B t_target and ket = tdof kt come rounded from the host: formed here, K2 - tdof kt would contract into one
+  // multiply-add and a chain at rest exactly on target would start to move
+  const double tf = 1.0 / p.t_period;
+#pragma unroll
+  for (int k = 0; k < ANI_MD_NH_MAXCHAIN; k++) {
+    const bool used = k < M;
+    eta[k] = used ? state[NS_ETA + k] : 0.0;
+    ed[k] = used ? state[NS_ETADOT + k] : 0.0;
+    edd[k] = used ? state[NS_ETADOTDOT + k] : 0.0;
+    Q[k] = (k == 0 ? ket : kt) / (tf * tf);
+  }
+  ed[ANI_MD_NH_MAXCHAIN] = 0.0;
+  const double nf = 1.0 / (double)p.nc_tchain, dfac = 1.0 - p.dt * p.drag / (double)p.nc_tchain;
+  const double h2 = nf * p.dt / 2.0, h4 = nf * p.dt / 4.0, h8 = nf * p.dt / 8.0;
+  edd[0] = (K2 - ket) / Q[0];
+  double s = 1.0;
+  for (int it = 0; it < p.nc_tchain; it++) {
+    for (int k = M - 1; k >= 1; k--) {
+      const double e = exp(-h8 * ed[k + 1]);
+      ed[k] = ((ed[k] * e + edd[k] * h4) * dfac) * e;
+    }
+    const double e0 = exp(-h8 * ed[1]);
+    ed[0] = ((ed[0] * e0 + edd[0] * h4) * dfac) * e0;
+    const double fac = exp(-h2 * ed[0]);
+    s *= fac;
+    K2 *= fac * fac;
+    edd[0] = (K2 - ket) / Q[0];
+    for (int k = 0; k < M; k++) eta[k] += h2 * ed[k];
+    ed[0] = (ed[0] * e0 + edd[0] * h4) * e0;
+    for (int k = 1; k < M; k++) {
+      const double e = exp(-h8 * ed[k + 1]);
+      ed[k] *= e;
+      edd[k] = (Q[k - 1] * ed[k - 1] * ed[k - 1] - kt) / Q[k];
+      ed[k] = (ed[k] + edd[k] * h4) * e;
+    }
+  }
+  double ec = ket * eta[0] + 0.5 * Q[0] * ed[0] * ed[0];
+  for (int k = 1; k < M; k++) ec += kt * eta[k] + 0.5 * Q[k] * ed[k] * ed[k];
+  state[NS_COUNT] += 1.0;
+  state[NS_K2] = K2;
+  state[NS_S] = s;
+  state[NS_ECOUPLE] = ec;
+#pragma unroll
+  for (int k = 0; k < ANI_MD_NH_MAXCHAIN; k++) {
+    state[NS_ETA + k] = eta[k];
+    state[NS_ETADOT + k] = ed[k];
+    state[NS_ETADOTDOT + k] = edd[k];
+  }
+}
+
+__global__ __launch_bounds__(256) void nh_scale_kernel(double* __restrict__ v, int n, const double* __restrict__ state) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < 3 * n) v[t] *= state[NS_S];
+}
+
+// initial_integrate_kernel with v = s v in front of it
+__global__ __launch_bounds__(256) void nh_initial_integrate_kernel(double* __restrict__ x, double* __restrict__ v,
+                                                                   const double* __restrict__ f, const double* __restrict__ dtfm,
+                                                                   double dt, int n, const double* __restrict__ xb,
+                                                                   double* __restrict__ d2max, const double* __restrict__ state) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double d2 = 0.0;
+  if (i < n) {
+    const double s = dtfm[i], sc = state[NS_S];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const double vk = fma(s, f[3 * i + k], sc * v[3 * i + k]);   // s v rounded, then the kick as initial_integrate_kernel contracts it
+      const double xk = x[3 * i + k] + dt * vk;
+      v[3 * i + k] = vk;
+      x[3 * i + k] = xk;
+      const double d = xk - xb[3 * i + k];
+      d2 += d * d;
+    }
+  }
+  __shared__ double red[4];
+  d2 = block_max(d2, red);   // as initial_integrate_kernel: at most one atomic per block, none once the maximum is larger
+  if (threadIdx.x == 0 && d2 > *reinterpret_cast<volatile double*>(d2max))
+    atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
+}
+
+// final_integrate_kernel without the thermostat term, and nh_kinetic_kernel on what it wrote
+__global__ __launch_bounds__(256) void nh_final_integrate_kernel(double* __restrict__ v, const double* __restrict__ f,
+                                                                 const double* __restrict__ dtfm, const double* __restrict__ mass,
+                                                                 int n, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double k2 = 0.0;
+  if (i < n) {
+    const double s = dtfm[i];
+    double vn[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      vn[k] = v[3 * (size_t)i + k] + s * f[3 * (size_t)i + k];
+      v[3 * (size_t)i + k] = vn[k];
+    }
+    k2 = k2_term(mass[i], vn[0], vn[1], vn[2]);
+  }
+  k2 = block_sum_fixed(k2, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = k2;
+}
+
+// part[c nblk + b] = K_c of block b, c = xx, yy, zz, xy, xz, yz
+__global__ __launch_bounds__(256) void thermo_reduce_kernel(const double* __restrict__ v, const double* __restrict__ mass, int n,
+                                                            double* __restrict__ part) {
+  __shared__ double red[4];
+  const int i = blockIdx.x * 256 + threadIdx.x, nblk = gridDim.x;
+  double k[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (i < n) {
+    const double m = mass[i], v0 = v[3 * (size_t)i], v1 = v[3 * (size_t)i + 1], v2 = v[3 * (size_t)i + 2];
+    k[0] = (m * v0 * v0) * NH_MVV2E; k[1] = (m * v1 * v1) * NH_MVV2E; k[2] = (m * v2 * v2) * NH_MVV2E;
+    k[3] = (m * v0 * v1) * NH_MVV2E; k[4] = (m * v0 * v2) * NH_MVV2E; k[5] = (m * v1 * v2) * NH_MVV2E;
+  }
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    const double sum = block_sum_fixed(k[c], red);
+    if (threadIdx.x == 0) part[c * nblk + blockIdx.x] = sum;
+  }
+}
+
+__global__ __launch_bounds__(256) void thermo_finish_kernel(const double* __restrict__ part, int nblk, const double* __restrict__ ev,
+                                                            int with_virial, double tdof, double volume,
+                                                            const double* __restrict__ nh_state, double* __restrict__ out) {
+  __shared__ double red[4];
+  double K[6];
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) a += part[c * nblk + b];
+    K[c] = block_sum_fixed(a, red);
+  }
+  if (threadIdx.x != 0) return;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double k2 = (K[0] + K[1]) + K[2], ke = 0.5 * k2, pe = ev[0];
+  const double ec = nh_state ? nh_state[NS_ECOUPLE] : 0.0;
+  out[0] = pe;
+  out[1] = ke;
+  out[2] = 2.0 * ke / (tdof * NH_BOLTZ);
+  // W_ab = ev[1 + 3 a + b]: xx, yy, zz at 1, 5, 9; xy, xz, yz at 2, 3, 6
+  const int wi[6] = {1, 5, 9, 2, 3, 6};
+  out[3] = with_virial ? (k2 + ((ev[1] + ev[5]) + ev[9])) / (3.0 * volume) * NH_NKTV2P : nan;
+#pragma unroll
+  for (int c = 0; c < 6; c++) out[4 + c] = with_virial ? (K[c] + ev[wi[c]]) / volume * NH_NKTV2P : nan;
+  out[10] = pe + ke;
+  out[11] = ec;
+  out[12] = (pe + ke) + ec;
+  out[13] = volume;
+  out[14] = k2;
+  out[15] = 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -840,5 +1033,67 @@ int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const do
   if (!x || !v || !cl || !w || !len3) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(rattle_velocities_kernel, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, cl, nc, w, len3[0],
                      len3[1], len3[2], periodic_mask);
+  return (int)hipGetLastError();
+}
+
+int ani_md_nh_work_size(int nlocal) { return nlocal > 0 ? (nlocal + 255) / 256 : 1; }
+
+int ani_md_nh_init(double* state, void* stream) {
+  if (!state) return (int)hipErrorInvalidValue;
+  return (int)hipMemsetAsync(state, 0, sizeof(double) * ANI_MD_NH_NSTATE, (hipStream_t)stream);
+}
+
+int ani_md_nh_kinetic(const double* v, const double* mass, int nlocal, double* work, void* stream) {
+  if (nlocal <= 0) return 0;
+  if (!v || !mass || !work) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(nh_kinetic_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, mass, nlocal, work);
+  return (int)hipGetLastError();
+}
+
+int ani_md_nh_chain(double* state, const double* work, int npart, double t_target, double tdof, const ani_md_nh_params* params,
+                    void* stream) {
+  if (!state || !params || npart < 0 || (npart > 0 && !work)) return (int)hipErrorInvalidValue;
+  if (params->mtchain < 1 || params->mtchain > ANI_MD_NH_MAXCHAIN || params->nc_tchain < 1 || !(params->t_period > 0.0) ||
+      !(params->dt > 0.0) || !(t_target > 0.0) || !(tdof > 0.0))
+    return (int)hipErrorInvalidValue;
+  const double kt = 0.0019872067 * t_target, ket = tdof * kt;
+  hipLaunchKernelGGL(nh_chain_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, work, npart, t_target, tdof, kt, ket, *params);
+  return (int)hipGetLastError();
+}
+
+int ani_md_nh_scale(double* v, int nlocal, const double* state, void* stream) {
+  if (nlocal <= 0) return 0;
+  if (!v || !state) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(nh_scale_kernel, dim3((3 * nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, nlocal, state);
+  return (int)hipGetLastError();
+}
+
+int ani_md_nh_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
+                                const double* x_built, double* d2max, const double* state, void* stream) {
+  if (nlocal <= 0) return 0;
+  if (!state) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(nh_initial_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, f, dtfm, dt,
+                     nlocal, x_built, d2max, state);
+  return (int)hipGetLastError();
+}
+
+int ani_md_nh_final_integrate(double* v, const double* f, const double* dtfm, const double* mass, int nlocal, double* work,
+                              void* stream) {
+  if (nlocal <= 0) return 0;
+  if (!mass || !work) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(nh_final_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, f, dtfm, mass,
+                     nlocal, work);
+  return (int)hipGetLastError();
+}
+
+int ani_md_thermo_work_size(int nlocal) { return 6 * (nlocal > 0 ? (nlocal + 255) / 256 : 1); }
+
+int ani_md_thermo(const double* v, const double* mass, int nlocal, const double* ev, int with_virial, double tdof, double volume,
+                  const double* nh_state, double* work, double* out, void* stream) {
+  if (!ev || !out || (nlocal > 0 && (!v || !mass || !work))) return (int)hipErrorInvalidValue;
+  const int nblk = nlocal > 0 ? (nlocal + 255) / 256 : 0;
+  if (nblk) hipLaunchKernelGGL(thermo_reduce_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, v, mass, nlocal, work);
+  hipLaunchKernelGGL(thermo_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, nblk, ev, with_virial, tdof, volume,
+                     nh_state, out);
   return (int)hipGetLastError();
 }

@@ -154,6 +154,8 @@ class VerletRun:
         self._cons = None      # bond constraints (set_constraints): None, or the device tables and parameters of the two stages
         self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
         self._rdf_every = 0    # radial distribution functions (set_rdf): 0 = none, else a frame every so many steps
+        self._nvt = None       # Nose-Hoover chain (set_nvt): None, or the device record, scratch and parameters
+        self._thermo_buf = None
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
             self._comm_stream = torch.cuda.current_stream(device) if os.environ.get("ANI_MD_OVERLAP_ONE_STREAM") else \
@@ -455,7 +457,12 @@ class VerletRun:
         self._forces()
 
     def step(self, force_rebuild: bool = False):
-        """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements)"""
+        """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements).  With a thermostat
+        (set_nvt) the step begins with a fresh kinetic sum and uses the current target: N calls agree with run(N) to the rounding of
+        that sum, not bitwise."""
+        if self._nvt is not None:
+            self._nvt_steps(1, self._nvt["t_target"], self._nvt["t_target"], force_rebuild)
+            return
         self._initial_integrate()
         if self._cons is not None:
             self._shake_positions()
@@ -468,12 +475,18 @@ class VerletRun:
         """``run N`` without per-step output: nothing looks at the full-step velocities between two steps, so the
         final_integrate of a step and the initial_integrate of the next are ONE kernel (same arithmetic and rounding as
         step() N times; the loop is in a full-step state again when this returns).  before_forces(k) / after_forces(k):
-        optional callables around the force evaluation of step k (the bench's phase-timer switches)."""
+        optional callables around the force evaluation of step k (the bench's phase-timer switches).  With a thermostat (set_nvt)
+        the steps are the separate launches described there, the target ramps from t_start to t_stop over the nsteps."""
         if nsteps <= 0:
             return
         if not self._fused:
             for _ in range(nsteps):
                 self.step()
+            return
+        if self._nvt is not None:
+            nvt = self._nvt
+            self._nvt_steps(int(nsteps), nvt["t_start"], nvt["t_stop"], False, before_forces, after_forces)
+            nvt["t_target"] = nvt["t_stop"]
             return
         cons = self._cons is not None
         self._initial_integrate()
@@ -571,6 +584,97 @@ class VerletRun:
                     energy_before=rec["e_first"], energy_after=rec["e_cur"], fnorm_before=rec["ff_first"] ** 0.5,
                     fnorm_after=rec["ff"] ** 0.5, force_evaluations=nevals, uphill_events=int(rec["uphill"]),
                     limited_moves=int(rec["limited"]), rebuilds=self.nbuilds - builds0)
+
+    # ---- Nose-Hoover chain ---------------------------------------------------------------------------------
+    def set_nvt(self, t_start, t_stop=None, t_period=None, mtchain: int = 3, nc_tchain: int = 1, drag: float = 0.0):
+        """``fix nvt temp t_start t_stop t_period`` (and the `temp` half of ``fix npt``): a Nose-Hoover chain of `mtchain` links at
+        constant volume, on the device (ani_md_nh_*, include/ani_md.h), fp64 whatever the handle.  t_stop None: t_start; t_period
+        None: 100 dt (fs); nc_tchain: sub-steps of the chain per half-step; drag: as ``fix_modify drag``.  set_nvt(None) clears the
+        thermostat: the loop launches what it launched before.  The chain starts at rest.
+        A step is then: chain half-step (its scale factor s stays on the device), ani_md_nh_initial_integrate (v = s v first),
+        [position stage], forces, ani_md_nh_final_integrate (which leaves the partial sums of sum m v^2), chain half-step on them,
+        ani_md_nh_scale -- with constraints: plain final integrate, velocity stage, ani_md_nh_kinetic, chain half-step, scale (a
+        uniform scale keeps r . (v_c - v_p) = 0).  3 N - 3 - nb degrees of freedom, nb the constrained bonds as they are when a step
+        runs.  Every run() and every step() call begins with a fresh ani_md_nh_kinetic of the velocities as they are (LAMMPS
+        computes the temperature in setup()), so velocities set by hand, by create_velocities or zeroed by minimize() never leave a
+        stale sum in the record; inside a run() the chain goes on from the sum it scaled itself.  step() N times and run(N)
+        therefore agree to the rounding of that sum, not bitwise.  In run(N) step k = 1..N has the target t_start + (k / N)
+        (t_stop - t_start) in both of its half-steps, every run() ramps anew, afterwards the target stays at t_stop; step() uses the
+        current target (t_start before the first run()).  The target is a kernel argument: the host reads nothing.
+        Raises with ``langevin``, with several ranks, for a temperature that is not positive and for mtchain outside 1..8."""
+        if t_start is None:
+            self._nvt = None
+            return
+        from . import ani_hip
+        if self.langevin is not None:
+            raise RuntimeError("VerletRun.set_nvt: the run has a Langevin thermostat (langevin=...); one temperature control at a time")
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.set_nvt: one rank only (the kinetic energy is not reduced over ranks)")
+        if not self._fused:
+            raise RuntimeError("VerletRun.set_nvt needs the device loop (the chain's kernels have no tensor-operation form)")
+        t_start = float(t_start)
+        t_stop = t_start if t_stop is None else float(t_stop)
+        t_period = 100.0 * self.dt if t_period is None else float(t_period)
+        if not (t_start > 0.0 and t_stop > 0.0 and np.isfinite(t_start) and np.isfinite(t_stop)):
+            raise ValueError("VerletRun.set_nvt: temperatures must be positive")
+        if not 1 <= int(mtchain) <= ani_hip.NH_MAXCHAIN:
+            raise ValueError(f"VerletRun.set_nvt: mtchain must be in 1..{ani_hip.NH_MAXCHAIN}")
+        if not (t_period > 0.0) or int(nc_tchain) < 1 or drag < 0.0:
+            raise ValueError("VerletRun.set_nvt: t_period > 0, nc_tchain >= 1 and drag >= 0")
+        if 3 * self.nlocal - 3 - self._ncons <= 0:
+            raise ValueError("VerletRun.set_nvt: no degrees of freedom")
+        par = ani_hip.NhParams(self.dt, t_period, float(drag), int(mtchain), int(nc_tchain))
+        state = torch.zeros(ani_hip.NH_NSTATE, dtype=torch.float64, device=self.device)
+        work = torch.empty(self._md.ani_md_nh_work_size(self.nlocal), dtype=torch.float64, device=self.device)
+        self._check(self._md.ani_md_nh_init(state.data_ptr(), self._stream))
+        self._nvt = dict(t_start=t_start, t_stop=t_stop, t_target=t_start, par=par, state=state, work=work,
+                         npart=(self.nlocal + 255) // 256, mass=self.mass[:, 0].contiguous(), mtchain=int(mtchain))
+
+    def _nvt_chain(self, t_target: float, npart: int):
+        nvt = self._nvt
+        self._check(self._md.ani_md_nh_chain(nvt["state"].data_ptr(), nvt["work"].data_ptr(), npart, t_target,
+                                             3.0 * self.nlocal - 3.0 - self._ncons, nvt["par"], self._stream))
+
+    def _nvt_kinetic(self):
+        nvt = self._nvt
+        self._check(self._md.ani_md_nh_kinetic(self.v.data_ptr(), nvt["mass"].data_ptr(), self.nlocal, nvt["work"].data_ptr(), self._stream))
+
+    def _nvt_steps(self, nsteps: int, t_from: float, t_to: float, force_rebuild: bool = False, before_forces=None, after_forces=None):
+        """nsteps thermostatted steps with the target going from t_from (exclusive) to t_to (at the last step)"""
+        nvt, md, st, n = self._nvt, self._md, self._stream, self.nlocal
+        cons = self._cons is not None
+        self._nvt_kinetic()                                   # the set-up of this call: the sum of the velocities as they are
+        for k in range(nsteps):
+            t = t_to if k + 1 == nsteps else t_from + ((k + 1) / nsteps) * (t_to - t_from)
+            self._nvt_chain(t, nvt["npart"] if k == 0 else 0)
+            self._check(md.ani_md_nh_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
+                                                       self.dt, n, self.x_built.data_ptr(), self._d2max.data_ptr(),
+                                                       nvt["state"].data_ptr(), st))
+            if cons:
+                self._shake_positions()
+            if before_forces is not None:
+                before_forces(k)
+            self._middle(force_rebuild)
+            if after_forces is not None:
+                after_forces(k)
+            if cons:
+                self._final_integrate()
+                self.project_velocities()
+                self._nvt_kinetic()
+            else:
+                self._check(md.ani_md_nh_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
+                                                         nvt["mass"].data_ptr(), n, nvt["work"].data_ptr(), st))
+            self._nvt_chain(t, nvt["npart"])
+            self._check(md.ani_md_nh_scale(self.v.data_ptr(), n, nvt["state"].data_ptr(), st))
+
+    def nvt_state(self) -> dict:
+        """the chain's device record (one synchronising read): half_steps, k2 (sum m v^2 after the last scaling, kcal/mol), s and
+        t_target of the last half-step, ecouple, tdof, nonfinite (half-steps that found a non-finite sum and did nothing), and
+        eta, eta_dot, eta_dotdot of the mtchain links"""
+        if self._nvt is None:
+            raise RuntimeError("VerletRun.nvt_state: no thermostat is set (set_nvt)")
+        from .ani_hip import nh_state_dict
+        return nh_state_dict(self._nvt["state"].cpu().numpy(), self._nvt["mtchain"])
 
     # ---- bond constraints ----------------------------------------------------------------------------------
     def set_constraints(self, bonds, lengths=None, tol: float = 1e-10, maxiter: int = 20, project: bool = True):
@@ -848,6 +952,33 @@ class VerletRun:
             else:
                 dist.all_reduce(w, group=self.group)
         return w.cpu().numpy().reshape(3, 3)
+
+    def thermo(self) -> dict:
+        """``thermo_style custom pe ke etotal temp press vol density`` from the device: one ani_md_thermo call (include/ani_md.h)
+        and one read.  Keys: pe, ke, etotal (kcal/mol), temp (K, on 3 N - 3 - nb degrees of freedom), press and pxx pyy pzz pxy pxz
+        pyz (atm: kinetic tensor plus the pair virial of the last force evaluation, over the box volume), vol (A^3), density
+        (g/cm^3), ecouple (the chain's energy, 0 without set_nvt) and econserve = etotal + ecouple.  The pressure entries are NaN
+        without ``vflag``, and while constraints are set (the constraint virial is not accumulated).  One rank on the device.  The
+        first call also sums the masses for the density, once."""
+        if self.dc.multi or not self._fused:
+            raise RuntimeError("VerletRun.thermo: one rank on the device only (the sums are not reduced over ranks)")
+        from . import ani_hip
+        n = self.nlocal
+        if self._thermo_buf is None or self._thermo_buf["n"] != n:
+            mass = self.mass[:, 0].contiguous()
+            self._thermo_buf = dict(n=n, mass=mass, mtot=float(mass.sum()),
+                                    work=torch.empty(self._md.ani_md_thermo_work_size(n), dtype=torch.float64, device=self.device),
+                                    out=torch.zeros(ani_hip.THERMO_N, dtype=torch.float64, device=self.device))
+        b = self._thermo_buf
+        vol = float(np.prod(self._box_len_np))
+        self._check(self._md.ani_md_thermo(self.v.data_ptr(), b["mass"].data_ptr(), n, self.ev.data_ptr(),
+                                           1 if (self.vflag and self._cons is None) else 0, 3.0 * n - 3.0 - self._ncons, vol,
+                                           self._nvt["state"].data_ptr() if self._nvt is not None else None, b["work"].data_ptr(),
+                                           b["out"].data_ptr(), self._stream))
+        rec = dict(zip(ani_hip.THERMO_KEYS, b["out"].cpu().tolist()))
+        del rec["k2"]
+        rec["density"] = b["mtot"] / vol / 0.602214129      # g/mol/A^3 -> g/cm^3 (LAMMPS units real, mv2d)
+        return rec
 
     def temperature(self, natoms_all: int) -> float:
         """LAMMPS compute temp: 2 KE / ((3 N - 3 - nb) k_B), nb the constrained bonds (set_constraints; 0 without)"""
