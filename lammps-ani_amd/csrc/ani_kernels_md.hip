@@ -7,6 +7,62 @@
 
 namespace {
 
+// ---- shared pieces ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_d(double a) { return a - a == 0.0; }
+
+// sum over the 256 threads of a block, the same order every time: xor butterflies inside a wave, then the four waves in order
+__device__ __forceinline__ double block_sum_fixed(double a, double* red) {
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+  __syncthreads();   // red may still be read from the call before
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ double block_max(double a, double* red) {
+  for (int off = 32; off > 0; off >>= 1) a = fmax(a, __shfl_xor(a, off));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// The displacement fold.  One thread of a workgroup hands in the workgroup's maximum: at most one atomic per workgroup -- and none
+// once the running maximum is larger (it only grows between two looks of the host: a stale read costs an atomic, never a missed
+// one).  1 563 same-address atomics made initial_integrate_kernel 21 us at 100 002 atoms.  Non-negative doubles order like their
+// bit patterns.
+__device__ __forceinline__ void raise_d2max(double d2, double* __restrict__ d2max) {
+  if (d2 > *reinterpret_cast<volatile double*>(d2max))
+    atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
+}
+// every thread's d2: workgroup maximum (one barrier), then raise_d2max by thread 0
+__device__ __forceinline__ void fold_d2max(double d2, double* __restrict__ d2max) {
+  for (int off = 32; off > 0; off >>= 1) d2 = fmax(d2, __shfl_xor(d2, off));
+  __shared__ double wmax[4];
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = d2;
+  __syncthreads();
+  if (threadIdx.x == 0) raise_d2max(fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3])), d2max);
+}
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+// fix langevin's random numbers: a key per (seed, step, atom), a uniform draw in [-0.5, 0.5) per component of it
+__device__ __forceinline__ unsigned long long langevin_key(unsigned long long seed, unsigned long long step, long long atom) {
+  return mix64(seed + 0x9E3779B97F4A7C15ULL * (step + 1)) ^ (0xD1B54A32D192ED03ULL * (unsigned long long)atom);
+}
+__device__ __forceinline__ double langevin_draw(unsigned long long key, int k) {
+  const unsigned long long h = mix64(key + 0x9E3779B97F4A7C15ULL * (k + 1));
+  return (double)(h >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+}
+
+// element t of an [n][3] block of doubles, as an offset into the array that the row index idx points into: 3 idx[t / 3] + t % 3
+__device__ __forceinline__ long long through3(const long long* __restrict__ idx, int t) {
+  const int g = t / 3, k = t - 3 * g;
+  return 3 * idx[g] + k;
+}
+
 __global__ __launch_bounds__(256) void initial_integrate_kernel(double* __restrict__ x, double* __restrict__ v,
                                                                 const double* __restrict__ f, const double* __restrict__ dtfm,
                                                                 double dt, int n, const double* __restrict__ xb,
@@ -25,24 +81,7 @@ __global__ __launch_bounds__(256) void initial_integrate_kernel(double* __restri
       d2 += d * d;
     }
   }
-  // workgroup maximum, then at most one atomic per workgroup -- and none once the running maximum is larger (it only
-  // grows between two looks of the host: a stale read costs an atomic, never a missed one).  1 563 same-address atomics
-  // made this kernel 21 us at 100 002 atoms.  Non-negative doubles order like their bit patterns.
-  for (int off = 32; off > 0; off >>= 1) d2 = fmax(d2, __shfl_xor(d2, off));
-  __shared__ double wmax[4];
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = d2;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    d2 = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
-    if (d2 > *reinterpret_cast<volatile double*>(d2max))
-      atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
-  }
-}
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
+  fold_d2max(d2, d2max);
 }
 
 __global__ __launch_bounds__(256) void final_integrate_kernel(double* __restrict__ v, double* __restrict__ f,
@@ -53,14 +92,13 @@ __global__ __launch_bounds__(256) void final_integrate_kernel(double* __restrict
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double s = dtfm[i];
-  const unsigned long long key = mix64(seed + 0x9E3779B97F4A7C15ULL * (step + 1)) ^ (0xD1B54A32D192ED03ULL * (unsigned long long)(tag ? tag[i] : i));
+  const unsigned long long key = langevin_key(seed, step, tag ? tag[i] : i);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     double fk = f[3 * i + k];
     const double vk = v[3 * i + k];
     if (langevin) {
-      const unsigned long long h = mix64(key + 0x9E3779B97F4A7C15ULL * (k + 1));
-      const double r = (double)(h >> 11) * (1.0 / 9007199254740992.0) - 0.5;   // uniform in [-0.5, 0.5)
+      const double r = langevin_draw(key, k);
       fk += g1[i] * vk + g2[i] * r;
       f[3 * i + k] = fk;
     }
@@ -80,14 +118,13 @@ __global__ __launch_bounds__(256) void final_initial_integrate_kernel(double* __
   double d2 = 0.0;
   if (i < n) {
     const double s = dtfm[i];
-    const unsigned long long key = mix64(seed + 0x9E3779B97F4A7C15ULL * (step + 1)) ^ (0xD1B54A32D192ED03ULL * (unsigned long long)(tag ? tag[i] : i));
+    const unsigned long long key = langevin_key(seed, step, tag ? tag[i] : i);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       double fk = f[3 * i + k];
       double vk = v[3 * i + k];
       if (langevin) {
-        const unsigned long long h = mix64(key + 0x9E3779B97F4A7C15ULL * (k + 1));
-        const double r = (double)(h >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+        const double r = langevin_draw(key, k);
         fk += g1[i] * vk + g2[i] * r;
         f[3 * i + k] = fk;
       }
@@ -100,50 +137,38 @@ __global__ __launch_bounds__(256) void final_initial_integrate_kernel(double* __
       d2 += d * d;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) d2 = fmax(d2, __shfl_xor(d2, off));
-  __shared__ double wmax[4];
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = d2;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    d2 = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
-    if (d2 > *reinterpret_cast<volatile double*>(d2max))
-      atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
-  }
+  fold_d2max(d2, d2max);
 }
 
 __global__ __launch_bounds__(256) void forward_ghosts_kernel(double* __restrict__ x, const long long* __restrict__ owner,
                                                              const double* __restrict__ shift, int nlocal, int nghost) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nghost) return;
-  const int g = t / 3, k = t - 3 * g;
-  x[3 * (size_t)nlocal + t] = x[3 * owner[g] + k] + shift[t];
+  x[3 * (size_t)nlocal + t] = x[through3(owner, t)] + shift[t];
 }
 
 __global__ __launch_bounds__(256) void pack_ghosts_kernel(const double* __restrict__ x, const long long* __restrict__ owner,
                                                           const double* __restrict__ shift, int nsend, double* __restrict__ out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nsend) return;
-  const int g = t / 3, k = t - 3 * g;
-  out[t] = x[3 * owner[g] + k] + shift[t];
+  out[t] = x[through3(owner, t)] + shift[t];
 }
 
 __global__ __launch_bounds__(256) void unpack_reverse_kernel(double* __restrict__ f, const long long* __restrict__ owner, int nsend,
                                                              const double* __restrict__ in) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nsend) return;
-  const int g = t / 3, k = t - 3 * g;
-  atomicAdd(&f[3 * owner[g] + k], in[t]);   // an atom can be a ghost of several bricks / images
+  atomicAdd(&f[through3(owner, t)], in[t]);   // an atom can be a ghost of several bricks / images
 }
 
 __global__ __launch_bounds__(256) void reverse_ghosts_kernel(double* __restrict__ f, const long long* __restrict__ owner,
                                                              int nlocal, int nghost) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nghost) return;
-  const int g = t / 3, k = t - 3 * g;
-  atomicAdd(&f[3 * owner[g] + k], f[3 * (size_t)nlocal + t]);
+  atomicAdd(&f[through3(owner, t)], f[3 * (size_t)nlocal + t]);
 }
 
-// the same with the ghost block in the caller's order: message slot g is ghost ghost_of[g]
+// the same with the ghost block in the caller's order: message slot g is ghost ghost_of[g] (two indices through one g: spelt out)
 __global__ __launch_bounds__(256) void reverse_ghosts_ordered_kernel(double* __restrict__ f, const long long* __restrict__ owner,
                                                                      const long long* __restrict__ ghost_of, int nlocal, int nghost) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,15 +182,14 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const double* __restri
                                                           double* __restrict__ out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * n) return;
-  const int g = t / 3, k = t - 3 * g;
-  out[t] = src[3 * idx[g] + k];
+  out[t] = src[through3(idx, t)];
 }
 __global__ __launch_bounds__(256) void scatter_rows_kernel(double* __restrict__ dst, const long long* __restrict__ idx, int n,
                                                            const double* __restrict__ in) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * n) return;
-  const int g = t / 3, k = t - 3 * g;
-  dst[3 * idx[g] + k] = in[t];
+  const long long o = through3(idx, t);
+  dst[o] = in[t];
 }
 
 
@@ -271,7 +295,8 @@ __global__ __launch_bounds__(256) void append_ghosts_kernel(double* __restrict__
   species[nlocal + g] = species[o];
 }
 // Neighbor::decide's look at the loop: *out = the running displacement maximum (then zeroed), or +inf when the last energy is not
-// finite (a capacity overflow or a blown-up step: the device entry points cannot return an error)
+// finite (a capacity overflow or a blown-up step: the device entry points cannot return an error).  fire_check_kernel has the same
+// three lines with finite_d for the test: the compiler does not fold `e == e` away, so one body would change one of the two.
 __global__ void check_kernel(double* __restrict__ d2max, const double* __restrict__ ev, double* __restrict__ out) {
   const double e = ev[0];
   const bool finite = e == e && e - e == 0.0;
@@ -290,23 +315,6 @@ enum { FS_ITER = 0, FS_DT, FS_ALPHA, FS_LASTNEG, FS_EPREV, FS_ECUR, FS_P, FS_VV,
        FS_EFIRST, FS_FFFIRST, FS_VMAX, FS_N };
 static_assert(FS_N == ANI_MD_FIRE_NSTATE, "state layout of include/ani_md.h");
 enum { FD_STOP = 0, FD_MOVE, FD_ITER, FD_DT, FD_ALPHA, FD_LASTNEG, FD_E, FD_P, FD_VV, FD_FF, FD_NUPHILL, FD_N = 16 };
-
-// sum over the 256 threads of a block, the same order every time: xor butterflies inside a wave, then the four waves in order
-__device__ __forceinline__ double block_sum_fixed(double a, double* red) {
-  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
-  __syncthreads();   // red may still be read from the call before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ double block_max(double a, double* red) {
-  for (int off = 32; off > 0; off >>= 1) a = fmax(a, __shfl_xor(a, off));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ __forceinline__ bool finite_d(double a) { return a - a == 0.0; }
 
 __global__ void fire_init_kernel(double* __restrict__ state, double dt0, double alpha0) {
   for (int k = 0; k < FS_N; k++) state[k] = 0.0;
@@ -438,9 +446,8 @@ __global__ __launch_bounds__(256) void fire_move_kernel(double* __restrict__ x, 
     if (dec[FD_ITER] == 1.0) { state[FS_EFIRST] = dec[FD_E]; state[FS_FFFIRST] = dec[FD_FF]; }
   }
   if (!d2max) return;
-  d2 = block_max(d2, red);   // as initial_integrate_kernel: at most one atomic per block, none once the maximum is larger
-  if (threadIdx.x == 0 && d2 > *reinterpret_cast<volatile double*>(d2max))
-    atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
+  d2 = block_max(d2, red);
+  if (threadIdx.x == 0) raise_d2max(d2, d2max);
 }
 
 // ani_md_check with the FIRE state record behind it: one pinned read of the host brings both
@@ -587,7 +594,8 @@ __global__ __launch_bounds__(256) void shake_positions_kernel(double* __restrict
       d2 = fmax(d2, dp2);
     }
   }
-  // workgroup reductions, then at most one integer atomic per word and workgroup (none once the running value is larger)
+  // workgroup reductions of d2 and the statistics together, then at most one integer atomic per word and workgroup (none once
+  // the running value is larger)
   for (int off = 32; off > 0; off >>= 1) {
     d2 = fmax(d2, __shfl_xor(d2, off));
     const unsigned it = __shfl_xor(iters, off);
@@ -604,11 +612,7 @@ __global__ __launch_bounds__(256) void shake_positions_kernel(double* __restrict
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  if (d2max && xb) {
-    d2 = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
-    if (d2 > *reinterpret_cast<volatile double*>(d2max))
-      atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
-  }
+  if (d2max && xb) raise_d2max(fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3])), d2max);
   if (!stats) return;
   unsigned long long res = wres[0];
   unsigned it = wit[0];
@@ -786,9 +790,8 @@ __global__ __launch_bounds__(256) void nh_initial_integrate_kernel(double* __res
     }
   }
   __shared__ double red[4];
-  d2 = block_max(d2, red);   // as initial_integrate_kernel: at most one atomic per block, none once the maximum is larger
-  if (threadIdx.x == 0 && d2 > *reinterpret_cast<volatile double*>(d2max))
-    atomicMax(reinterpret_cast<unsigned long long*>(d2max), (unsigned long long)__double_as_longlong(d2));
+  d2 = block_max(d2, red);
+  if (threadIdx.x == 0) raise_d2max(d2, d2max);
 }
 
 // final_integrate_kernel without the thermostat term, and nh_kinetic_kernel on what it wrote
@@ -861,129 +864,114 @@ __global__ __launch_bounds__(256) void thermo_finish_kernel(const double* __rest
   out[15] = 0.0;
 }
 
+// ---- launches ---------------------------------------------------------------------------------------------------------------
+// everything goes on the caller's stream; blocks(count) workgroups of 256 threads unless an entry point says otherwise
+inline dim3 blocks(int count) { return dim3((count + 255) / 256); }
+inline int nblocks(int nlocal) { return nlocal > 0 ? (nlocal + 255) / 256 : 1; }
+inline const long long* ll(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+inline long long* ll(int64_t* p) { return reinterpret_cast<long long*>(p); }
+
+template <typename K, typename... A>
+void enqueue(K kernel, dim3 grid, int block, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, (hipStream_t)stream, args...);
+}
+template <typename K, typename... A>
+int launch(K kernel, dim3 grid, int block, void* stream, A... args) {
+  enqueue(kernel, grid, block, stream, args...);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
 
 int ani_md_gather_rows(const double* src, const int64_t* idx, int n, double* out, void* stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream, src,
-                     reinterpret_cast<const long long*>(idx), n, out);
-  return (int)hipGetLastError();
+  return launch(gather_rows_kernel, blocks(3 * n), 256, stream, src, ll(idx), n, out);
 }
 
 int ani_md_scatter_rows(double* dst, const int64_t* idx, int n, const double* in, void* stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dst,
-                     reinterpret_cast<const long long*>(idx), n, in);
-  return (int)hipGetLastError();
+  return launch(scatter_rows_kernel, blocks(3 * n), 256, stream, dst, ll(idx), n, in);
 }
 
 int ani_md_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
                              const double* x_built, double* d2max, void* stream) {
   if (nlocal <= 0) return 0;
-  hipLaunchKernelGGL(initial_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, f, dtfm, dt,
-                     nlocal, x_built, d2max);
-  return (int)hipGetLastError();
+  return launch(initial_integrate_kernel, blocks(nlocal), 256, stream, x, v, f, dtfm, dt, nlocal, x_built, d2max);
 }
 
 int ani_md_final_integrate(double* v, double* f, const double* dtfm, int nlocal, int langevin, const double* g1,
                            const double* g2, const int64_t* tag, uint64_t seed, uint64_t step, void* stream) {
   if (nlocal <= 0) return 0;
-  hipLaunchKernelGGL(final_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, f, dtfm, nlocal,
-                     langevin, g1, g2, reinterpret_cast<const long long*>(tag), (unsigned long long)seed, (unsigned long long)step);
-  return (int)hipGetLastError();
+  return launch(final_integrate_kernel, blocks(nlocal), 256, stream, v, f, dtfm, nlocal, langevin, g1, g2, ll(tag),
+                (unsigned long long)seed, (unsigned long long)step);
 }
 
 int ani_md_final_initial_integrate(double* x, double* v, double* f, const double* dtfm, double dt, int nlocal, int langevin,
                                    const double* g1, const double* g2, const int64_t* tag, uint64_t seed, uint64_t step,
                                    const double* x_built, double* d2max, void* stream) {
   if (nlocal <= 0) return 0;
-  hipLaunchKernelGGL(final_initial_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, f, dtfm, dt,
-                     nlocal, langevin, g1, g2, reinterpret_cast<const long long*>(tag), (unsigned long long)seed,
-                     (unsigned long long)step, x_built, d2max);
-  return (int)hipGetLastError();
+  return launch(final_initial_integrate_kernel, blocks(nlocal), 256, stream, x, v, f, dtfm, dt, nlocal, langevin, g1, g2, ll(tag),
+                (unsigned long long)seed, (unsigned long long)step, x_built, d2max);
 }
 
 int ani_md_forward_ghosts(double* x, const int64_t* owner, const double* shift, int nlocal, int nghost, void* stream) {
   if (nghost <= 0) return 0;
-  hipLaunchKernelGGL(forward_ghosts_kernel, dim3((3 * nghost + 255) / 256), dim3(256), 0, (hipStream_t)stream, x,
-                     reinterpret_cast<const long long*>(owner), shift, nlocal, nghost);
-  return (int)hipGetLastError();
+  return launch(forward_ghosts_kernel, blocks(3 * nghost), 256, stream, x, ll(owner), shift, nlocal, nghost);
 }
 
 int ani_md_reverse_ghosts(double* f, const int64_t* owner, int nlocal, int nghost, void* stream) {
   if (nghost <= 0) return 0;
-  hipLaunchKernelGGL(reverse_ghosts_kernel, dim3((3 * nghost + 255) / 256), dim3(256), 0, (hipStream_t)stream, f,
-                     reinterpret_cast<const long long*>(owner), nlocal, nghost);
-  return (int)hipGetLastError();
+  return launch(reverse_ghosts_kernel, blocks(3 * nghost), 256, stream, f, ll(owner), nlocal, nghost);
 }
 
 int ani_md_reverse_ghosts_ordered(double* f, const int64_t* owner, const int64_t* ghost_of, int nlocal, int nghost, void* stream) {
   if (nghost <= 0) return 0;
   if (!ghost_of) return ani_md_reverse_ghosts(f, owner, nlocal, nghost, stream);
-  hipLaunchKernelGGL(reverse_ghosts_ordered_kernel, dim3((3 * nghost + 255) / 256), dim3(256), 0, (hipStream_t)stream, f,
-                     reinterpret_cast<const long long*>(owner), reinterpret_cast<const long long*>(ghost_of), nlocal, nghost);
-  return (int)hipGetLastError();
+  return launch(reverse_ghosts_ordered_kernel, blocks(3 * nghost), 256, stream, f, ll(owner), ll(ghost_of), nlocal, nghost);
 }
 
 int ani_md_pack_ghosts(const double* x, const int64_t* owner, const double* shift, int nsend, double* out, void* stream) {
   if (nsend <= 0) return 0;
-  hipLaunchKernelGGL(pack_ghosts_kernel, dim3((3 * nsend + 255) / 256), dim3(256), 0, (hipStream_t)stream, x,
-                     reinterpret_cast<const long long*>(owner), shift, nsend, out);
-  return (int)hipGetLastError();
+  return launch(pack_ghosts_kernel, blocks(3 * nsend), 256, stream, x, ll(owner), shift, nsend, out);
 }
 
 int ani_md_unpack_reverse(double* f, const int64_t* owner, int nsend, const double* in, void* stream) {
   if (nsend <= 0) return 0;
-  hipLaunchKernelGGL(unpack_reverse_kernel, dim3((3 * nsend + 255) / 256), dim3(256), 0, (hipStream_t)stream, f,
-                     reinterpret_cast<const long long*>(owner), nsend, in);
-  return (int)hipGetLastError();
+  return launch(unpack_reverse_kernel, blocks(3 * nsend), 256, stream, f, ll(owner), nsend, in);
 }
-
-}  // extern "C"
 
 int ani_md_wrap_positions(double* x, int n, const double* lo3, const double* len3, int periodic_mask, void* stream) {
   if (n <= 0 || !periodic_mask) return 0;
-  hipLaunchKernelGGL(wrap_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, n, lo3[0], lo3[1], lo3[2], len3[0], len3[1],
-                     len3[2], periodic_mask);
-  return (int)hipGetLastError();
+  return launch(wrap_kernel, blocks(3 * n), 256, stream, x, n, lo3[0], lo3[1], lo3[2], len3[0], len3[1], len3[2], periodic_mask);
 }
 
 int ani_md_ghost_shell_count(const double* x, int n, const double* clo, const double* chi, int ncombo, int* blk_cnt, int* blk_off,
                              int* out_counts, void* stream) {
   if (ncombo <= 0) return 0;
-  const int nblk = n > 0 ? (n + 255) / 256 : 1;
-  hipLaunchKernelGGL(shell_count_kernel, dim3(nblk, ncombo), dim3(256), 0, (hipStream_t)stream, x, n, clo, chi, nblk, blk_cnt);
-  hipLaunchKernelGGL(shell_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, blk_cnt, blk_off, ncombo, nblk, out_counts);
-  return (int)hipGetLastError();
+  const int nblk = nblocks(n);
+  enqueue(shell_count_kernel, dim3(nblk, ncombo), 256, stream, x, n, clo, chi, nblk, blk_cnt);
+  return launch(shell_scan_kernel, dim3(1), 1024, stream, blk_cnt, blk_off, ncombo, nblk, out_counts);
 }
 
 int ani_md_ghost_shell_fill(const double* x, int n, const double* clo, const double* chi, const double* cshift, int ncombo,
                             const int* blk_off, int64_t* send_idx, double* send_shift, void* stream) {
   if (ncombo <= 0) return 0;
-  const int nblk = n > 0 ? (n + 255) / 256 : 1;
-  hipLaunchKernelGGL(shell_fill_kernel, dim3(nblk, ncombo), dim3(256), 0, (hipStream_t)stream, x, n, clo, chi, cshift, nblk, blk_off,
-                     reinterpret_cast<long long*>(send_idx), send_shift);
-  return (int)hipGetLastError();
+  const int nblk = nblocks(n);
+  return launch(shell_fill_kernel, dim3(nblk, ncombo), 256, stream, x, n, clo, chi, cshift, nblk, blk_off, ll(send_idx), send_shift);
 }
 
 int ani_md_append_ghosts(double* x, int* species, int nlocal, const int64_t* owner, const double* shift, int nghost, void* stream) {
   if (nghost <= 0) return 0;
-  hipLaunchKernelGGL(append_ghosts_kernel, dim3((nghost + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, species, nlocal,
-                     reinterpret_cast<const long long*>(owner), shift, nghost);
-  return (int)hipGetLastError();
+  return launch(append_ghosts_kernel, blocks(nghost), 256, stream, x, species, nlocal, ll(owner), shift, nghost);
 }
 
 int ani_md_check(double* d2max, const double* ev, double* out, void* stream) {
-  hipLaunchKernelGGL(check_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d2max, ev, out);
-  return (int)hipGetLastError();
+  return launch(check_kernel, dim3(1), 1, stream, d2max, ev, out);
 }
 
-int ani_md_fire_work_size(int nlocal) {
-  const int nblk = nlocal > 0 ? (nlocal + 255) / 256 : 1;
-  return FD_N + 4 * nblk;
-}
+int ani_md_fire_work_size(int nlocal) { return FD_N + 4 * nblocks(nlocal); }
 
 int ani_md_fire_init(double* state, double* v, int nlocal, const ani_md_fire_params* p, void* stream) {
   if (!state || !p) return (int)hipErrorInvalidValue;
@@ -991,8 +979,7 @@ int ani_md_fire_init(double* state, double* v, int nlocal, const ani_md_fire_par
     const hipError_t rc = hipMemsetAsync(v, 0, sizeof(double) * 3 * (size_t)nlocal, (hipStream_t)stream);
     if (rc != hipSuccess) return (int)rc;
   }
-  hipLaunchKernelGGL(fire_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, p->dt0, p->alpha0);
-  return (int)hipGetLastError();
+  return launch(fire_init_kernel, dim3(1), 1, stream, state, p->dt0, p->alpha0);
 }
 
 int ani_md_fire_iterate(double* x, double* v, const double* f, const double* fm, int nlocal, const double* ev,
@@ -1000,20 +987,17 @@ int ani_md_fire_iterate(double* x, double* v, const double* f, const double* fm,
                         void* stream) {
   if (nlocal <= 0) return 0;
   if (!p || !state || !work) return (int)hipErrorInvalidValue;
-  const int nblk = (nlocal + 255) / 256;
+  const int nblk = nblocks(nlocal);
   double* dec = work;
   double* part = work + FD_N;
   double* vmaxp = part + 3 * nblk;
-  const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(fire_reduce_kernel, dim3(nblk), dim3(256), 0, st, v, f, nlocal, state, part);
-  hipLaunchKernelGGL(fire_velocity_kernel, dim3(nblk), dim3(256), 0, st, x, v, f, fm, nlocal, ev, *p, state, part, dec, vmaxp);
-  hipLaunchKernelGGL(fire_move_kernel, dim3(nblk), dim3(256), 0, st, x, v, nlocal, p->dmax, dec, vmaxp, state, x_built, d2max);
-  return (int)hipGetLastError();
+  enqueue(fire_reduce_kernel, dim3(nblk), 256, stream, v, f, nlocal, state, part);
+  enqueue(fire_velocity_kernel, dim3(nblk), 256, stream, x, v, f, fm, nlocal, ev, *p, state, part, dec, vmaxp);
+  return launch(fire_move_kernel, dim3(nblk), 256, stream, x, v, nlocal, p->dmax, dec, vmaxp, state, x_built, d2max);
 }
 
 int ani_md_fire_check(double* d2max, const double* ev, const double* state, double* out, void* stream) {
-  hipLaunchKernelGGL(fire_check_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d2max, ev, state, out);
-  return (int)hipGetLastError();
+  return launch(fire_check_kernel, dim3(1), 1, stream, d2max, ev, state, out);
 }
 
 int ani_md_shake_positions(double* x, double* v, const int* cl, const double* d, int nc, const double* w, double dt, double tol,
@@ -1021,9 +1005,8 @@ int ani_md_shake_positions(double* x, double* v, const int* cl, const double* d,
                            unsigned long long* stats, void* stream) {
   if (nc <= 0) return 0;
   if (!x || !cl || !d || !w || !len3 || !(dt > 0.0)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(shake_positions_kernel, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, cl, d, nc, w, dt, tol,
-                     maxiter, len3[0], len3[1], len3[2], periodic_mask, x_built, d2max, stats);
-  return (int)hipGetLastError();
+  return launch(shake_positions_kernel, blocks(nc), 256, stream, x, v, cl, d, nc, w, dt, tol, maxiter, len3[0], len3[1], len3[2],
+                periodic_mask, x_built, d2max, stats);
 }
 
 int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const double* d, int nc, const double* w,
@@ -1031,12 +1014,10 @@ int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const do
   (void)d;
   if (nc <= 0) return 0;
   if (!x || !v || !cl || !w || !len3) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(rattle_velocities_kernel, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, cl, nc, w, len3[0],
-                     len3[1], len3[2], periodic_mask);
-  return (int)hipGetLastError();
+  return launch(rattle_velocities_kernel, blocks(nc), 256, stream, x, v, cl, nc, w, len3[0], len3[1], len3[2], periodic_mask);
 }
 
-int ani_md_nh_work_size(int nlocal) { return nlocal > 0 ? (nlocal + 255) / 256 : 1; }
+int ani_md_nh_work_size(int nlocal) { return nblocks(nlocal); }
 
 int ani_md_nh_init(double* state, void* stream) {
   if (!state) return (int)hipErrorInvalidValue;
@@ -1046,8 +1027,7 @@ int ani_md_nh_init(double* state, void* stream) {
 int ani_md_nh_kinetic(const double* v, const double* mass, int nlocal, double* work, void* stream) {
   if (nlocal <= 0) return 0;
   if (!v || !mass || !work) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(nh_kinetic_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, mass, nlocal, work);
-  return (int)hipGetLastError();
+  return launch(nh_kinetic_kernel, blocks(nlocal), 256, stream, v, mass, nlocal, work);
 }
 
 int ani_md_nh_chain(double* state, const double* work, int npart, double t_target, double tdof, const ani_md_nh_params* params,
@@ -1057,43 +1037,37 @@ int ani_md_nh_chain(double* state, const double* work, int npart, double t_targe
       !(params->dt > 0.0) || !(t_target > 0.0) || !(tdof > 0.0))
     return (int)hipErrorInvalidValue;
   const double kt = 0.0019872067 * t_target, ket = tdof * kt;
-  hipLaunchKernelGGL(nh_chain_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, work, npart, t_target, tdof, kt, ket, *params);
-  return (int)hipGetLastError();
+  return launch(nh_chain_kernel, dim3(1), 256, stream, state, work, npart, t_target, tdof, kt, ket, *params);
 }
 
 int ani_md_nh_scale(double* v, int nlocal, const double* state, void* stream) {
   if (nlocal <= 0) return 0;
   if (!v || !state) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(nh_scale_kernel, dim3((3 * nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, nlocal, state);
-  return (int)hipGetLastError();
+  return launch(nh_scale_kernel, blocks(3 * nlocal), 256, stream, v, nlocal, state);
 }
 
 int ani_md_nh_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
                                 const double* x_built, double* d2max, const double* state, void* stream) {
   if (nlocal <= 0) return 0;
   if (!state) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(nh_initial_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, v, f, dtfm, dt,
-                     nlocal, x_built, d2max, state);
-  return (int)hipGetLastError();
+  return launch(nh_initial_integrate_kernel, blocks(nlocal), 256, stream, x, v, f, dtfm, dt, nlocal, x_built, d2max, state);
 }
 
 int ani_md_nh_final_integrate(double* v, const double* f, const double* dtfm, const double* mass, int nlocal, double* work,
                               void* stream) {
   if (nlocal <= 0) return 0;
   if (!mass || !work) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(nh_final_integrate_kernel, dim3((nlocal + 255) / 256), dim3(256), 0, (hipStream_t)stream, v, f, dtfm, mass,
-                     nlocal, work);
-  return (int)hipGetLastError();
+  return launch(nh_final_integrate_kernel, blocks(nlocal), 256, stream, v, f, dtfm, mass, nlocal, work);
 }
 
-int ani_md_thermo_work_size(int nlocal) { return 6 * (nlocal > 0 ? (nlocal + 255) / 256 : 1); }
+int ani_md_thermo_work_size(int nlocal) { return 6 * nblocks(nlocal); }
 
 int ani_md_thermo(const double* v, const double* mass, int nlocal, const double* ev, int with_virial, double tdof, double volume,
                   const double* nh_state, double* work, double* out, void* stream) {
   if (!ev || !out || (nlocal > 0 && (!v || !mass || !work))) return (int)hipErrorInvalidValue;
   const int nblk = nlocal > 0 ? (nlocal + 255) / 256 : 0;
-  if (nblk) hipLaunchKernelGGL(thermo_reduce_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, v, mass, nlocal, work);
-  hipLaunchKernelGGL(thermo_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, nblk, ev, with_virial, tdof, volume,
-                     nh_state, out);
-  return (int)hipGetLastError();
+  if (nblk) enqueue(thermo_reduce_kernel, dim3(nblk), 256, stream, v, mass, nlocal, work);
+  return launch(thermo_finish_kernel, dim3(1), 256, stream, work, nblk, ev, with_virial, tdof, volume, nh_state, out);
 }
+
+}  // extern "C"

@@ -103,6 +103,7 @@ class VerletRun:
         self.ani, self.device, self.group = ani, device, group
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.dt, self.cutneigh, self.skin, self.every = float(dt), cutoff + skin, skin, int(every)
+        self._d2_rebuild = (0.5 * skin) ** 2   # Neighbor::check_distance: rebuild once an atom has moved more than skin/2
         box_lo = np.zeros(3) if box_lo is None else np.asarray(box_lo, dtype=np.float64)
         self._box_lo_np = box_lo
         self._box_len_np = np.asarray(box_len, dtype=np.float64)
@@ -110,7 +111,6 @@ class VerletRun:
                              native=native_comm, force_collectives=force_collectives)
         self.native = native_comm
         self.vflag = bool(vflag)
-        self.ex = self.dc   # the exchange object (forward_positions / reverse_add)
         self.masses = torch.as_tensor(np.asarray(masses, dtype=np.float64), device=device)
         self.langevin = langevin
         n = inp.nlocal
@@ -166,17 +166,23 @@ class VerletRun:
         self._post_force()
 
     # ---- pieces of the loop ---------------------------------------------------------------------------
-    def _allreduce_max(self, t: torch.Tensor) -> float:
-        if self.native is not None and self.dc.multi:
-            self.native.allreduce(t.data_ptr(), t.numel(), "max", stream=self._stream)
-            return float(t)
-        if dist.is_initialized() and (dist.get_world_size(self.group) > 1 or self.dc.multi):
+    def _allreduce(self, t: torch.Tensor, op: str) -> torch.Tensor:
+        """t reduced over the ranks (op: "sum" or "max"), in place where it can be: inside libani_hip.so with a native
+        communicator, through a host copy under gloo (which takes no device tensor), torch.distributed otherwise.  With one
+        participant (one rank, or force_collectives) every form leaves the values as they are."""
+        if self.native is not None and self.dc.multi and t.is_cuda and t.dtype == torch.float64:
+            self.native.allreduce(t.data_ptr(), t.numel(), op, stream=self._stream)
+        elif dist.is_initialized() and (dist.get_world_size(self.group) > 1 or self.dc.multi):
             if dist.get_backend(self.group) == "gloo" and t.is_cuda:
-                c = t.cpu()
-                dist.all_reduce(c, op=dist.ReduceOp.MAX, group=self.group)
-                return float(c)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-        return float(t)
+                t = t.cpu()
+            dist.all_reduce(t, op=dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def _allreduce_max(self, t: torch.Tensor) -> float:
+        return float(self._allreduce(t, "max"))
+
+    def _allreduce_sum(self, t: torch.Tensor) -> float:
+        return float(self._allreduce(t, "sum"))
 
     def _per_atom_factors(self):
         """mass-dependent factors of the integrator, expanded once per re-neighbouring (atoms may have migrated) so
@@ -314,22 +320,8 @@ class VerletRun:
             self.f.zero_()
         self.ani.compute_device(self.ntotal, self.nlocal, None, self.x.data_ptr(), self.npairs, None, None, None, 1,
                                 self.f.data_ptr(), self.ev.data_ptr(), vflag=self.vflag, stream=self._stream)
-        if self._fold:
-            pass   # the finish kernel has added the images' rows into their owners'
-        elif self._fused and not self.dc.multi:
-            self._check(self._md.ani_md_reverse_ghosts(self.f.data_ptr(), self.dc.send_idx.data_ptr(), self.nlocal,
-                                                       self.ntotal - self.nlocal, self._stream))
-        elif self._fused and self.native is not None:
-            self.native.reverse(self.f.data_ptr(), self.nlocal, stream=self._stream)
-        elif self._fused:
-            dc, ns = self.dc, int(self.dc.send_idx.numel())
-            if self._recvbuf.shape[0] != ns:
-                self._recvbuf = torch.empty((ns, 3), dtype=torch.float64, device=self.device)
-            dc._a2a(self.f[self.nlocal:], dc.send_splits, dc.recv_splits, out=self._recvbuf)
-            self._check(self._md.ani_md_unpack_reverse(self.f.data_ptr(), dc.send_idx.data_ptr(), ns, self._recvbuf.data_ptr(),
-                                                       self._stream))
-        else:
-            self.dc.reverse_add(self.f)
+        if not self._fold:   # folded: the finish kernel has added the images' rows into their owners'
+            self._reverse_ghosts()
 
     def _post_force(self):
         """fix langevin (LAMMPS fix_langevin.cpp, uniform random numbers in [-0.5, 0.5)): f += g1 v + g2 r on owned atoms.
@@ -368,67 +360,209 @@ class VerletRun:
         t_now = 2.0 * ke / (3.0 * n - 3.0 - self._ncons) / BOLTZ
         self.v *= (T / t_now) ** 0.5
 
-    def _allreduce_sum(self, t: torch.Tensor) -> float:
-        if self.native is not None and self.dc.multi and t.is_cuda and t.dtype == torch.float64:
-            self.native.allreduce(t.data_ptr(), t.numel(), "sum", stream=self._stream)
-            return float(t)
-        if dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            if dist.get_backend(self.group) == "gloo" and t.is_cuda:
-                c = t.cpu()
-                dist.all_reduce(c, group=self.group)
-                return float(c)
-            dist.all_reduce(t, group=self.group)
-        return float(t)
-
-    def _initial_integrate(self):
-        # fix nve initial_integrate: v += dtf f / m ; x += dt v  (fused: + the displacement maximum of check_distance)
-        if self._fused:
+    # ---- the schedule of a step: first half, middle, second half ---------------------------------------
+    def _first_half(self, t_target=None, npart: int = 0):
+        """fix nve / fix nvt initial_integrate: v += dtf f / m ; x += dt v  (fused: + the displacement maximum of check_distance),
+        behind the chain's half-step with a thermostat (v = s v first); then the position stage of the constraints"""
+        nvt = self._nvt
+        if nvt is not None:
+            self._nvt_chain(t_target, npart)
+            self._check(self._md.ani_md_nh_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
+                                                             self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
+                                                             self._d2max.data_ptr(), nvt["state"].data_ptr(), self._stream))
+        elif self._fused:
             self._check(self._md.ani_md_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
                                                           self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
                                                           self._d2max.data_ptr(), self._stream))
         else:
             self.v.addcmul_(self.f[: self.nlocal], self._dtf_over_m)
             self.x[: self.nlocal].add_(self.v, alpha=self.dt)
+        if self._cons is not None:
+            self._shake_positions()
 
     def _middle(self, force_rebuild: bool = False):
         """between the two integrator halves: re-neighbouring decision, ghost positions, forces, ghost forces"""
         self.step_no += 1
         self.since_build += 1
         # Neighbor::decide + check_distance (every N steps, rebuild if any atom moved more than skin/2)
-        rebuild = bool(force_rebuild)
-        if not rebuild and self.since_build % self.every == 0:
-            if self._native_rebuild:
-                # one kernel and one pinned read: the running maximum (or +inf when the last energy is not finite), then zeroed
-                self._check(self._md.ani_md_check(self._d2max.data_ptr(), self.ev.data_ptr(), self._chk_dev.data_ptr(), self._stream))
-                self._chk_host.copy_(self._chk_dev, non_blocking=True)
-                torch.cuda.current_stream(self.device).synchronize()
-                worst = float(self._chk_host[0])
-                if worst == float("inf"):
-                    raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
-                                       "capacity (ANI_ERR_CAPACITY) or the forces diverged")
-                if self._cons is not None:
-                    self._constraint_health(self._chk_host[1:])   # the stats words sit behind the maximum: the same read
-                rebuild = worst > (0.5 * self.skin) ** 2
-                d2 = None
-            elif self._fused:
-                d2 = self._d2max.clone()    # running maximum since the last look (monotone between rebuilds: same decision)
-                self._d2max.zero_()
-            else:
-                d2 = (self.x[: self.nlocal] - self.x_built).square().sum(1).max().reshape(1) if self.nlocal else \
-                    torch.zeros(1, dtype=torch.float64, device=self.device)
-            if d2 is not None:
-                # the same host round trip carries the health of the last force evaluation: the device entry point cannot
-                # return ANI_ERR_CAPACITY (nothing synchronises), it turns the energy into NaN instead
-                d2 = torch.where(torch.isfinite(self.ev[:1]), d2, torch.full_like(d2, float("inf")))
-                worst = self._allreduce_max(d2.clone())
-                if worst == float("inf"):
-                    raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
-                                       "capacity (ANI_ERR_CAPACITY) or the forces diverged")
-                rebuild = worst > (0.5 * self.skin) ** 2
+        rebuild = bool(force_rebuild) or (self.since_build % self.every == 0 and self._look() > self._d2_rebuild)
         self._ghosts_and_forces(rebuild)
         # on every path above the ghost rows of x are now the images of this step's owned positions
         if self._rdf_every and self.step_no % self._rdf_every == 0:
             self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
+
+    def _second_half(self, t_target=None):
+        """fix langevin post_force + fix nve final_integrate and the velocity stage of the constraints; with a thermostat the
+        pass that also leaves the partial sums of sum m v^2 (constrained: the plain one, the velocity stage, then the sums), the
+        chain's half-step on them and the scaling (a uniform scale keeps r . (v_c - v_p) = 0)"""
+        nvt = self._nvt
+        if nvt is None or self._cons is not None:
+            self._final_integrate()
+            self.project_velocities()
+            if nvt is not None:
+                self._nvt_kinetic()
+        else:
+            self._check(self._md.ani_md_nh_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
+                                                           nvt["mass"].data_ptr(), self.nlocal, nvt["work"].data_ptr(), self._stream))
+        if nvt is not None:
+            self._nvt_chain(t_target, nvt["npart"])
+            self._check(self._md.ani_md_nh_scale(self.v.data_ptr(), self.nlocal, nvt["state"].data_ptr(), self._stream))
+
+    def _steps(self, nsteps: int, t_from=None, t_to=None, force_rebuild: bool = False, before_forces=None, after_forces=None):
+        """nsteps steps of first half, middle, second half; with a thermostat the target goes from t_from (exclusive) to t_to (at
+        the last step), and the call begins with the sum of the velocities as they are.  The one exception to the three pieces:
+        where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints,
+        the device loop -- the two are ONE launch, which carries the number of the step that ends."""
+        nvt = self._nvt
+        one_launch = self._fused and nvt is None and self._cons is None
+        t = None
+        if nvt is not None:
+            self._nvt_kinetic()
+        for k in range(nsteps):
+            if nvt is not None:
+                t = t_to if k + 1 == nsteps else t_from + ((k + 1) / nsteps) * (t_to - t_from)
+            if k == 0 or not one_launch:
+                self._first_half(t, nvt["npart"] if nvt is not None and k == 0 else 0)   # later steps: the sum the chain scaled itself
+            if before_forces is not None:
+                before_forces(k)
+            self._middle(force_rebuild)
+            if after_forces is not None:
+                after_forces(k)
+            if one_launch and k + 1 < nsteps:
+                lang = self._g1 is not None
+                self._check(self._md.ani_md_final_initial_integrate(
+                    self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.dt, self.nlocal,
+                    1 if lang else 0, self._g1.data_ptr() if lang else None, self._g2.data_ptr() if lang else None,
+                    self.tag.data_ptr(), self._seed, self.step_no, self.x_built.data_ptr(), self._d2max.data_ptr(), self._stream))
+            else:
+                self._second_half(t)
+
+    def step(self, force_rebuild: bool = False):
+        """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements).  With a thermostat
+        (set_nvt) the step begins with a fresh kinetic sum and uses the current target: N calls agree with run(N) to the rounding of
+        that sum, not bitwise."""
+        t = self._nvt["t_target"] if self._nvt is not None else None
+        self._steps(1, t, t, force_rebuild)
+
+    def run(self, nsteps: int, before_forces=None, after_forces=None):
+        """``run N`` without per-step output: nothing looks at the full-step velocities between two steps, so the
+        final_integrate of a step and the initial_integrate of the next are ONE kernel (same arithmetic and rounding as
+        step() N times; the loop is in a full-step state again when this returns).  before_forces(k) / after_forces(k):
+        optional callables around the force evaluation of step k (the bench's phase-timer switches).  With a thermostat (set_nvt)
+        or constraints the halves are the separate launches of step(); the thermostat's target ramps from t_start to t_stop over
+        the nsteps."""
+        if nsteps <= 0:
+            return
+        if not self._fused:
+            for _ in range(nsteps):
+                self.step()
+            return
+        nvt = self._nvt
+        if nvt is None:
+            self._steps(int(nsteps), None, None, False, before_forces, after_forces)
+        else:
+            self._steps(int(nsteps), nvt["t_start"], nvt["t_stop"], False, before_forces, after_forces)
+            nvt["t_target"] = nvt["t_stop"]
+
+    # ---- the host's look at the device ---------------------------------------------------------------------------------
+    def _look(self, extra=None, word=None) -> float:
+        """The worst squared displacement of an owned atom since the last look, which this zeroes; raises when the last energy is
+        not finite -- the device entry point cannot return ANI_ERR_CAPACITY (nothing synchronises), it turns the energy into NaN
+        instead, and this host round trip carries that along -- and, with constraints, when a cluster solve did not converge (the
+        stats words sit behind the maximum: the same read).  With native re-neighbouring one kernel and one pinned read;
+        otherwise the tensor form and an all-reduce over the ranks.  extra: (state, device words, pinned words) of minimize(),
+        whose check kernel puts the FIRE record behind the maximum; minimize() judges the two together, with on_look in between.
+        word: a scratch word in place of the loop's own maximum (warm_paths: nothing is zeroed that the loop needs, nothing is
+        judged)."""
+        d2max = self._d2max if word is None else word
+        if self._native_rebuild:
+            if extra is None:
+                dev, host = self._chk_dev, self._chk_host
+                self._check(self._md.ani_md_check(d2max.data_ptr(), self.ev.data_ptr(), dev.data_ptr(), self._stream))
+            else:
+                state, dev, host = extra
+                self._check(self._md.ani_md_fire_check(d2max.data_ptr(), self.ev.data_ptr(), state.data_ptr(), dev.data_ptr(), self._stream))
+            host.copy_(dev, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            worst = float(host[0])    # the running maximum, or +inf when the last energy is not finite
+        else:
+            if self._fused:
+                d2 = d2max.clone()    # running maximum since the last look (monotone between rebuilds: same decision)
+                d2max.zero_()
+            else:
+                d2 = (self.x[: self.nlocal] - self.x_built).square().sum(1).max().reshape(1) if self.nlocal else \
+                    torch.zeros(1, dtype=torch.float64, device=self.device)
+            d2 = torch.where(torch.isfinite(self.ev[:1]), d2, torch.full_like(d2, float("inf")))
+            worst = self._allreduce_max(d2.clone())
+        if extra is not None or word is not None:
+            return worst
+        if worst == float("inf"):
+            raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
+                               "capacity (ANI_ERR_CAPACITY) or the forces diverged")
+        if self._cons is not None and self._native_rebuild:
+            self._constraint_health(self._chk_host[1:])
+        return worst
+
+    # ---- ghost exchanges ------------------------------------------------------------------------------------------------
+    def _msgbuf(self, name: str, rows: int) -> torch.Tensor:
+        """the send or receive buffer of the all-to-all exchanges (name: _sendbuf / _recvbuf), made anew when the count changed"""
+        buf = getattr(self, name)
+        if buf.shape[0] != rows:
+            buf = torch.empty((rows, 3), dtype=torch.float64, device=self.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _forward_ghosts(self, stream):
+        """forward exchange: x[nlocal:] <- the owners' positions (+ image shifts); kernels and native messages on `stream`, the
+        all-to-all on torch's current stream"""
+        dc = self.dc
+        if not self._fused:
+            dc.forward_positions(self.x)
+        elif not dc.multi:
+            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(),
+                                                       self.nlocal, self.ntotal - self.nlocal, stream))
+        elif self.native is not None:
+            self.native.forward(self.x.data_ptr(), self.nlocal, stream=stream)
+        else:
+            # several ranks: one pack kernel, the all-to-all receives straight into the ghost block of x
+            ns = int(dc.send_idx.numel())
+            buf = self._msgbuf("_sendbuf", ns)
+            self._check(self._md.ani_md_pack_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(), ns,
+                                                    buf.data_ptr(), stream))
+            dc._a2a(buf, dc.recv_splits, dc.send_splits, out=self.x[self.nlocal:])
+
+    def _reverse_send(self, stream):
+        """first half of the reverse exchange on the device: the ghost rows of f travel to their owners' ranks (one rank: they are
+        here already)"""
+        dc = self.dc
+        if not dc.multi:
+            return
+        if self.native is not None:
+            self.native.reverse_send(self.f.data_ptr(), self.nlocal, stream=stream)
+        else:
+            dc._a2a(self.f[self.nlocal:], dc.send_splits, dc.recv_splits, out=self._msgbuf("_recvbuf", int(dc.send_idx.numel())))
+
+    def _reverse_unpack(self, stream):
+        """second half: what arrived is added into the owners' rows (an atom can be a ghost of several bricks / images)"""
+        dc = self.dc
+        if not dc.multi:
+            self._check(self._md.ani_md_reverse_ghosts(self.f.data_ptr(), dc.send_idx.data_ptr(), self.nlocal,
+                                                       self.ntotal - self.nlocal, stream))
+        elif self.native is not None:
+            self.native.reverse_unpack(self.f.data_ptr(), stream=stream)
+        else:
+            self._check(self._md.ani_md_unpack_reverse(self.f.data_ptr(), dc.send_idx.data_ptr(), int(dc.send_idx.numel()),
+                                                       self._recvbuf.data_ptr(), stream))
+
+    def _reverse_ghosts(self):
+        """reverse exchange of the ghost forces on the loop's stream, both halves back to back"""
+        if not self._fused:
+            self.dc.reverse_add(self.f)
+        elif self.dc.multi and self.native is not None:
+            self.native.reverse(self.f.data_ptr(), self.nlocal, stream=self._stream)   # both halves; one kernel with one participant
+        else:
+            self._reverse_send(self._stream)
+            self._reverse_unpack(self._stream)
 
     def _ghosts_and_forces(self, rebuild: bool):
         """re-neighbouring or forward ghost positions, then forces and reverse ghost forces, by whichever path the loop is on"""
@@ -437,82 +571,9 @@ class VerletRun:
         elif self._overlap:
             self._forces_overlapped()
             return
-        elif self._fold:
-            pass   # the pack kernel of the step reads the images' positions from their owners (and writes them to x)
-        elif self._fused and not self.dc.multi:
-            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), self.dc.send_idx.data_ptr(), self.dc.send_shift.data_ptr(),
-                                                       self.nlocal, self.ntotal - self.nlocal, self._stream))
-        elif self._fused and self.native is not None:
-            self.native.forward(self.x.data_ptr(), self.nlocal, stream=self._stream)
-        elif self._fused:
-            # several ranks: one pack kernel, the all-to-all receives straight into the ghost block of x
-            dc, ns = self.dc, int(self.dc.send_idx.numel())
-            if self._sendbuf.shape[0] != ns:
-                self._sendbuf = torch.empty((ns, 3), dtype=torch.float64, device=self.device)
-            self._check(self._md.ani_md_pack_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(), ns,
-                                                    self._sendbuf.data_ptr(), self._stream))
-            dc._a2a(self._sendbuf, dc.recv_splits, dc.send_splits, out=self.x[self.nlocal:])
-        else:
-            self.dc.forward_positions(self.x)
+        elif not self._fold:   # folded: the pack kernel of the step reads the images' positions from their owners (and writes them to x)
+            self._forward_ghosts(self._stream)
         self._forces()
-
-    def step(self, force_rebuild: bool = False):
-        """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements).  With a thermostat
-        (set_nvt) the step begins with a fresh kinetic sum and uses the current target: N calls agree with run(N) to the rounding of
-        that sum, not bitwise."""
-        if self._nvt is not None:
-            self._nvt_steps(1, self._nvt["t_target"], self._nvt["t_target"], force_rebuild)
-            return
-        self._initial_integrate()
-        if self._cons is not None:
-            self._shake_positions()
-        self._middle(force_rebuild)
-        self._final_integrate()
-        if self._cons is not None:
-            self.project_velocities()
-
-    def run(self, nsteps: int, before_forces=None, after_forces=None):
-        """``run N`` without per-step output: nothing looks at the full-step velocities between two steps, so the
-        final_integrate of a step and the initial_integrate of the next are ONE kernel (same arithmetic and rounding as
-        step() N times; the loop is in a full-step state again when this returns).  before_forces(k) / after_forces(k):
-        optional callables around the force evaluation of step k (the bench's phase-timer switches).  With a thermostat (set_nvt)
-        the steps are the separate launches described there, the target ramps from t_start to t_stop over the nsteps."""
-        if nsteps <= 0:
-            return
-        if not self._fused:
-            for _ in range(nsteps):
-                self.step()
-            return
-        if self._nvt is not None:
-            nvt = self._nvt
-            self._nvt_steps(int(nsteps), nvt["t_start"], nvt["t_stop"], False, before_forces, after_forces)
-            nvt["t_target"] = nvt["t_stop"]
-            return
-        cons = self._cons is not None
-        self._initial_integrate()
-        if cons:
-            self._shake_positions()
-        for k in range(nsteps):
-            if before_forces is not None:
-                before_forces(k)
-            self._middle()
-            if after_forces is not None:
-                after_forces(k)
-            if cons:
-                # the velocity stage stands between the two halves: the separate launches of step(), same arithmetic
-                self._final_integrate()
-                self.project_velocities()
-                if k + 1 < nsteps:
-                    self._initial_integrate()
-                    self._shake_positions()
-            elif k + 1 == nsteps:
-                self._final_integrate()
-            else:
-                lang = self._g1 is not None
-                self._check(self._md.ani_md_final_initial_integrate(
-                    self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.dt, self.nlocal,
-                    1 if lang else 0, self._g1.data_ptr() if lang else None, self._g2.data_ptr() if lang else None,
-                    self.tag.data_ptr(), self._seed, self.step_no, self.x_built.data_ptr(), self._d2max.data_ptr(), self._stream))
 
     def minimize(self, etol: float, ftol: float, maxiter: int, dt0=None, check_every=None, on_look=None, **fire_params):
         """``min_style fire`` + ``minimize etol ftol maxiter``: FIRE energy minimisation of the owned atoms without leaving the
@@ -563,10 +624,7 @@ class VerletRun:
             rebuild = False
             # the stop by maxiter falls in call maxiter + 1 at the latest: that look ends the loop whatever check_every is
             if calls % every == 0 or calls == maxiter + 1:
-                self._check(md.ani_md_fire_check(self._d2max.data_ptr(), self.ev.data_ptr(), state.data_ptr(), chk_dev.data_ptr(), st))
-                chk_host.copy_(chk_dev, non_blocking=True)
-                torch.cuda.current_stream(self.device).synchronize()
-                worst = float(chk_host[0])
+                worst = self._look(extra=(state, chk_dev, chk_host))
                 rec = dict(zip(ani_hip.FIRE_STATE_KEYS, chk_host[1:].tolist()))
                 if on_look is not None:
                     on_look(rec)
@@ -576,7 +634,7 @@ class VerletRun:
                                        "kernels' LDS capacity (ANI_ERR_CAPACITY) or the forces diverged")
                 if rec["stop"] != 0.0:
                     break
-                rebuild = worst > (0.5 * self.skin) ** 2
+                rebuild = worst > self._d2_rebuild
             self._ghosts_and_forces(rebuild)
             nevals += 1
         self.v.zero_()
@@ -591,11 +649,9 @@ class VerletRun:
         constant volume, on the device (ani_md_nh_*, include/ani_md.h), fp64 whatever the handle.  t_stop None: t_start; t_period
         None: 100 dt (fs); nc_tchain: sub-steps of the chain per half-step; drag: as ``fix_modify drag``.  set_nvt(None) clears the
         thermostat: the loop launches what it launched before.  The chain starts at rest.
-        A step is then: chain half-step (its scale factor s stays on the device), ani_md_nh_initial_integrate (v = s v first),
-        [position stage], forces, ani_md_nh_final_integrate (which leaves the partial sums of sum m v^2), chain half-step on them,
-        ani_md_nh_scale -- with constraints: plain final integrate, velocity stage, ani_md_nh_kinetic, chain half-step, scale (a
-        uniform scale keeps r . (v_c - v_p) = 0).  3 N - 3 - nb degrees of freedom, nb the constrained bonds as they are when a step
-        runs.  Every run() and every step() call begins with a fresh ani_md_nh_kinetic of the velocities as they are (LAMMPS
+        Where the chain's half-steps stand in a step: _first_half / _second_half and DESIGN.md §3.5 (the scale factor s stays on the
+        device).  3 N - 3 - nb degrees of freedom, nb the constrained bonds as they are when a step runs.
+        Every run() and every step() call begins with a fresh ani_md_nh_kinetic of the velocities as they are (LAMMPS
         computes the temperature in setup()), so velocities set by hand, by create_velocities or zeroed by minimize() never leave a
         stale sum in the record; inside a run() the chain goes on from the sum it scaled itself.  step() N times and run(N)
         therefore agree to the rounding of that sum, not bitwise.  In run(N) step k = 1..N has the target t_start + (k / N)
@@ -639,34 +695,6 @@ class VerletRun:
         nvt = self._nvt
         self._check(self._md.ani_md_nh_kinetic(self.v.data_ptr(), nvt["mass"].data_ptr(), self.nlocal, nvt["work"].data_ptr(), self._stream))
 
-    def _nvt_steps(self, nsteps: int, t_from: float, t_to: float, force_rebuild: bool = False, before_forces=None, after_forces=None):
-        """nsteps thermostatted steps with the target going from t_from (exclusive) to t_to (at the last step)"""
-        nvt, md, st, n = self._nvt, self._md, self._stream, self.nlocal
-        cons = self._cons is not None
-        self._nvt_kinetic()                                   # the set-up of this call: the sum of the velocities as they are
-        for k in range(nsteps):
-            t = t_to if k + 1 == nsteps else t_from + ((k + 1) / nsteps) * (t_to - t_from)
-            self._nvt_chain(t, nvt["npart"] if k == 0 else 0)
-            self._check(md.ani_md_nh_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
-                                                       self.dt, n, self.x_built.data_ptr(), self._d2max.data_ptr(),
-                                                       nvt["state"].data_ptr(), st))
-            if cons:
-                self._shake_positions()
-            if before_forces is not None:
-                before_forces(k)
-            self._middle(force_rebuild)
-            if after_forces is not None:
-                after_forces(k)
-            if cons:
-                self._final_integrate()
-                self.project_velocities()
-                self._nvt_kinetic()
-            else:
-                self._check(md.ani_md_nh_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
-                                                         nvt["mass"].data_ptr(), n, nvt["work"].data_ptr(), st))
-            self._nvt_chain(t, nvt["npart"])
-            self._check(md.ani_md_nh_scale(self.v.data_ptr(), n, nvt["state"].data_ptr(), st))
-
     def nvt_state(self) -> dict:
         """the chain's device record (one synchronising read): half_steps, k2 (sum m v^2 after the last scaling, kcal/mol), s and
         t_target of the last half-step, ecouple, tdof, nonfinite (half-steps that found a non-finite sum and did nothing), and
@@ -682,9 +710,9 @@ class VerletRun:
         ani_md_rattle_velocities, include/ani_md.h).  bonds: [nb, 2] global tags; lengths: [nb] in A (None: the current
         minimum-image distances); tol: bound on | |r|^2 - d^2 | / d^2 of every bond after the position stage; maxiter: Newton
         iterations per cluster and step.  The host builds the clusters (``constraint_clusters``: stars of a centre and one to
-        three partners, ValueError otherwise).  From here on step() runs initial, position stage, forces, final, velocity stage
-        and run() makes the same launches; every look of the host (the displacement check) brings the stage's statistics along
-        and raises when a cluster did not converge.  project: run the position stage once on the positions as they are (old and
+        three partners, ValueError otherwise).  From here on the two stages stand behind the two halves of every step
+        (_first_half / _second_half), in step() and run() alike; every look of the host (the displacement check)
+        brings the stage's statistics along and raises when a cluster did not converge.  project: run the position stage once on the positions as they are (old and
         new positions the same, no velocity written), then the velocity stage, and -- with lengths given, which moves atoms --
         evaluate the forces again.  An empty bond list clears the constraints: the loop launches what it launched before.
         temperature() and create_velocities count 3 N - 3 - nb degrees of freedom.  One rank with native re-neighbouring only
@@ -770,33 +798,16 @@ class VerletRun:
             raise RuntimeError("VerletRun.constraint_stats: no constraints are set")
         return self._stats_record(self._chk_dev[1:].cpu())
 
-    def _pack_and_send_ghosts(self):
-        """forward exchange on the current stream: x[nlocal:] <- the owners' positions (+ image shifts)"""
-        dc = self.dc
-        if not dc.multi:
-            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(),
-                                                       self.nlocal, self.ntotal - self.nlocal, torch.cuda.current_stream(self.device).cuda_stream))
-            return
-        if self.native is not None:
-            self.native.forward(self.x.data_ptr(), self.nlocal, stream=torch.cuda.current_stream(self.device).cuda_stream)
-            return
-        ns = int(dc.send_idx.numel())
-        if self._sendbuf.shape[0] != ns:
-            self._sendbuf = torch.empty((ns, 3), dtype=torch.float64, device=self.device)
-        self._check(self._md.ani_md_pack_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(), ns,
-                                                self._sendbuf.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
-        dc._a2a(self._sendbuf, dc.recv_splits, dc.send_splits, out=self.x[self.nlocal:])
-
     def _forces_overlapped(self):
         """Forward exchange, PairANI::compute and reverse exchange of a step that keeps its list, the two exchanges on the
         communication stream: the forward one beside the rows without ghosts (pack, compaction, AEV forward), the reverse
         one beside their backward pass (ani_step_begin / ani_step_ghosts_ready / ani_step_finish)."""
-        s1, s2, ev, dc = torch.cuda.current_stream(self.device), self._comm_stream, self._ev, self.dc
+        s1, s2, ev = torch.cuda.current_stream(self.device), self._comm_stream, self._ev
         nl, nt = self.nlocal, self.ntotal
         ev[0].record(s1)                                   # initial_integrate has moved the owned atoms
         with torch.cuda.stream(s2):
             s2.wait_event(ev[0])
-            self._pack_and_send_ghosts()
+            self._forward_ghosts(torch.cuda.current_stream(self.device).cuda_stream)
             ev[1].record(s2)
         self.ani.step_begin(nt, nl, self.x.data_ptr(), self.f.data_ptr(), self.ev.data_ptr(), stream=s1.cuda_stream)
         s1.wait_event(ev[1])                               # ghost positions are in place
@@ -804,23 +815,11 @@ class VerletRun:
         ev[2].record(s1)                                   # ghost rows of f are final
         with torch.cuda.stream(s2):
             s2.wait_event(ev[2])
-            if dc.multi and self.native is not None:
-                self.native.reverse_send(self.f.data_ptr(), nl, stream=s2.cuda_stream)
-            elif dc.multi:
-                ns = int(dc.send_idx.numel())
-                if self._recvbuf.shape[0] != ns:
-                    self._recvbuf = torch.empty((ns, 3), dtype=torch.float64, device=self.device)
-                dc._a2a(self.f[nl:], dc.send_splits, dc.recv_splits, out=self._recvbuf)
+            self._reverse_send(s2.cuda_stream)
             ev[3].record(s2)
         self.ani.step_finish(stream=s1.cuda_stream)
         s1.wait_event(ev[3])
-        if dc.multi and self.native is not None:
-            self.native.reverse_unpack(self.f.data_ptr(), stream=s1.cuda_stream)
-        elif dc.multi:
-            self._check(self._md.ani_md_unpack_reverse(self.f.data_ptr(), dc.send_idx.data_ptr(), int(dc.send_idx.numel()),
-                                                       self._recvbuf.data_ptr(), s1.cuda_stream))
-        else:   # one rank: the owners are here, the ghost rows are added once the owned rows are written
-            self._check(self._md.ani_md_reverse_ghosts(self.f.data_ptr(), dc.send_idx.data_ptr(), nl, nt - nl, s1.cuda_stream))
+        self._reverse_unpack(s1.cuda_stream)   # one rank: the owners are here, the ghost rows are added once the owned rows are written
 
     def _final_integrate(self):
         # fix langevin post_force + fix nve final_integrate
@@ -838,19 +837,8 @@ class VerletRun:
         """Run once, without touching the trajectory, the pieces of the loop that only some steps execute — the displacement
         check with its host round trip — so that their first-use costs (module loads of the tensor kernels, lazily made
         buffers) fall before a caller's timed region whatever its number of warm-up steps."""
-        if self._native_rebuild:
-            scratch = torch.zeros(1, dtype=torch.float64, device=self.device)   # not the loop's own maximum: the kernel zeroes it
-            self._check(self._md.ani_md_check(scratch.data_ptr(), self.ev.data_ptr(), self._chk_dev.data_ptr(), self._stream))
-            self._chk_host.copy_(self._chk_dev, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            return
-        if self._fused:
-            d2 = self._d2max.clone()
-        else:
-            d2 = (self.x[: self.nlocal] - self.x_built).square().sum(1).max().reshape(1) if self.nlocal else \
-                torch.zeros(1, dtype=torch.float64, device=self.device)
-        d2 = torch.where(torch.isfinite(self.ev[:1]), d2, torch.full_like(d2, float("inf")))
-        self._allreduce_max(d2.clone())
+        # not on the loop's own maximum: a look zeroes its word
+        self._look(word=torch.zeros(1, dtype=torch.float64, device=self.device))
 
     # ---- analysis ----------------------------------------------------------------------------------------
     def find_molecules(self, formula_cap: int = 4096):
@@ -864,11 +852,8 @@ class VerletRun:
         from .ani_hip import AniError, formula_dict
         n, ng, st = self.nlocal, self.ntotal - self.nlocal, self._stream
         owner = self.dc.send_idx
-        if ng and self._fused:
-            # the ghost rows of x as images of the owned atoms' positions of this moment (a step's first kernel does the same)
-            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), owner.data_ptr(), self.dc.send_shift.data_ptr(), n, ng, st))
-        elif ng:
-            self.dc.forward_positions(self.x)
+        if ng:
+            self._forward_ghosts(st)   # the ghost rows of x as images of the owned atoms' positions of this moment
         S = len(self.ani.species_symbols())
         mol = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
         rows = torch.zeros((int(formula_cap), S + 1), dtype=torch.int32, device=self.device)
@@ -900,20 +885,12 @@ class VerletRun:
         self.ani.rdf_configure(int(nbins), self.cutneigh - self.skin if rmax is None else float(rmax), pairs)
         self._rdf_every = int(every)
 
-    def _refresh_ghosts(self):
-        """the ghost rows of x as images of the owned atoms' positions of this moment (a step's first kernel does the same)"""
-        n, ng = self.nlocal, self.ntotal - self.nlocal
-        if ng and self._fused:
-            self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), self.dc.send_idx.data_ptr(), self.dc.send_shift.data_ptr(),
-                                                       n, ng, self._stream))
-        elif ng:
-            self.dc.forward_positions(self.x)
-
     def sample_rdf(self):
         """one frame now, on the current positions (whatever `every` says)"""
         if self.ani.rdf_config() is None:
             raise RuntimeError("VerletRun.sample_rdf: no RDF is set (set_rdf)")
-        self._refresh_ghosts()
+        if self.ntotal > self.nlocal:
+            self._forward_ghosts(self._stream)   # the ghost rows of x as images of the owned atoms' positions of this moment
         self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
 
     def rdf(self, reset: bool = False) -> dict:
@@ -943,15 +920,7 @@ class VerletRun:
         """the pair style's virial of the last force evaluation, summed over ranks (kcal/mol, row-major 3x3; needs vflag)"""
         if not self.vflag:
             raise RuntimeError("VerletRun was made without vflag")
-        w = self.ev[1:10].clone()
-        if dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            if dist.get_backend(self.group) == "gloo" and w.is_cuda:
-                c = w.cpu()
-                dist.all_reduce(c, group=self.group)
-                w = c
-            else:
-                dist.all_reduce(w, group=self.group)
-        return w.cpu().numpy().reshape(3, 3)
+        return self._allreduce(self.ev[1:10].clone(), "sum").cpu().numpy().reshape(3, 3)
 
     def thermo(self) -> dict:
         """``thermo_style custom pe ke etotal temp press vol density`` from the device: one ani_md_thermo call (include/ani_md.h)

@@ -10,10 +10,10 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?run on a GPU box through
 OUT=gpurun_out/profile_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 ARGS="--full --no-cpu-baseline --no-dense-pass --no-extra --steps 40 --warmup 5"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit
 for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_LDS_IDX_ACTIVE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16"; do
   tag=$(echo $c | cut -d' ' -f1)
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p --output-format csv -- python bench.py $ARGS > /dev/null 2> $OUT/pmc_$tag.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p --output-format csv -- python bench.py $ARGS > /dev/null 2> $OUT/pmc_$tag.err || exit   # nothing more on a card after a pass that failed
 done
 python - "$OUT" <<'PY'
 import csv, glob, collections, json, sys, os
