@@ -244,6 +244,72 @@ int ani_md_thermo_work_size(int nlocal);
 int ani_md_thermo(const double* v, const double* mass, int nlocal, const double* ev, int with_virial, double tdof, double volume,
                   const double* nh_state, double* work, double* out, void* stream);
 
+/*
+ * Isotropic Nose-Hoover barostat on top of the chain above (LAMMPS `fix npt temp ... iso ...` with `mtk yes` and pchain > 0: Martyna,
+ * Tobias, Klein, J. Chem. Phys. 101 (1994) 4177; the integrator of Tuckerman et al., J. Phys. A 39 (2006) 5629).  fp64 whatever the
+ * handle, one rank, no floating-point atomics, nothing synchronises.  The box lives in the barostat record on the device; the host
+ * reads it where it looks anyway (ani_md_npt_check).
+ *
+ * Notation: N owned atoms; tdof, kt = k_B t_target, K2 as above; Wtr = (ev[1] + ev[5]) + ev[9], the pair virial of the last force
+ * evaluation; V = len[0] len[1] len[2] of the record; W = ((N + 1) kt) (p_period p_period); wd the one scalar strain rate (the three
+ * equal strain rates of `iso`); c the fixed point of the dilation, the box centre at ani_md_npt_init.
+ *
+ * Barostat chain: the chain half-step above -- the same device function -- on K2 := W wd^2 with tdof := 1 (ket = kt), t_period :=
+ * p_period, drag := 0, M := mpchain, nc := nc_pchain and the barostat's own eta, eta_dot, eta_dotdot; then wd *= s.  The barostat has
+ * no drag.
+ * Strain-rate update:  P = (K2 + Wtr) / (3 V) nktv2p;   wd += dt/2 [ (P - p_target) V / nktv2p + K2 / (3 N) ] / W.
+ *
+ * First half (ani_md_npt_chain phase 0, then ani_md_npt_initial_integrate):
+ *   1. barostat chain    2. thermostat chain on K2, giving s; K2 *= s^2 (the chain does it)    3. strain-rate update with that K2
+ *   4. fv = exp(-dt/2 wd (1 + 1/N)),  mu = exp(dt/2 wd)
+ *   5. per atom:  v = (s fv) v;  v += dtfm f;  x = c + mu (x - c);  x += dt v;  x = c + mu (x - c)
+ *   6. box:  lo = c + mu^2 (lo - c),  len *= mu^2;  ratio[k] = len_new[k] / len_old[k];  omega += dt wd
+ *   7. every ghost shift row *= ratio, per component (shifts are set exactly at every re-neighbouring: the rounding of this product
+ *      does not accumulate beyond one list epoch)
+ * Second half (ani_md_npt_final_integrate, ani_md_npt_chain phase 1, ani_md_nh_scale):
+ *   1. per atom:  v += dtfm f;  v *= fv  (the fv of the record: the same wd as the first half), and the partials of K2 in the same pass
+ *   2. K2 summed in the fixed order    3. strain-rate update with the new K2 and the new Wtr    4. thermostat chain, then v *= s
+ *   5. barostat chain
+ * This is FixNH's order for iso, mtk yes, pchain > 0.
+ *
+ * Conserved:  pe + ke + ecouple(thermostat, NH record [4]) + ecouple(barostat, record [21]) with
+ *   ecouple(barostat) = 3 (W wd^2 / 2 + ecouple of the barostat chain) + p_target (V - V0) / nktv2p,   V0 the volume at ani_md_npt_init.
+ * The factor 3: the three equal strain rates are one scalar here.
+ *
+ * Barostat record: ANI_MD_NPT_NSTATE doubles on the device:
+ *   [0] half-steps done   [1] wd   [2] omega = sum dt wd   [3] P of the last strain-rate update   [4] its p_target   [5] W   [6] fv   [7] mu
+ *   [8..11) box lo   [11..14) box len   [14..17) ratio of the last first half   [17..20) c   [20] V0   [21] ecouple(barostat)
+ *   [22] half-steps that found K2, Wtr or the new wd non-finite   [23] N   [24..32) eta   [32..40) eta_dot   [40..48) eta_dotdot of the
+ *   barostat chain (unused links stay 0)   [48] ecouple of the barostat chain alone   [49] V   [50..56) 0
+ * A half-step that finds K2, Wtr or the new wd non-finite writes s = 1 into the NH record as ani_md_nh_chain does (with [1], [3], [5],
+ * one more in [6]), fv = mu = 1 and ratio = 1 into this one, adds one to [22] and leaves [0], the box, wd and both chains.
+ *
+ * ani_md_npt_init       fills the record: lo, len, c = lo + len / 2, V0 = V, N, fv = mu = ratio = 1, the rest 0 (host arguments).
+ * ani_md_npt_chain      one workgroup.  phase 0: steps 1-4 and 6 of the first half; phase 1: steps 2-5 of the second.  npart > 0: K2 =
+ *                       the partials in the fixed order of ani_md_nh_chain; npart == 0: K2 = nh_state[1].  Writes both records.
+ *                       t_target and p_target (atm) are arguments: the host ramps them and reads nothing.  params: host pointer.
+ * ani_md_npt_initial_integrate   step 5 on rows [0, nlocal) with the displacement fold of ani_md_initial_integrate against x_built
+ *                       (which is NOT rescaled: the displacement includes the dilation), and step 7 on shift rows [0, nghost), in one
+ *                       launch over nlocal + nghost rows.
+ * ani_md_npt_final_integrate     step 1 of the second half; work: the partials of ani_md_nh_kinetic on the new velocities, bit for bit.
+ * ani_md_npt_check      ani_md_check with the barostat record behind the word: out[1 + j] = npt_state[j]
+ *                       (out: 1 + ANI_MD_NPT_NSTATE doubles).
+ */
+#define ANI_MD_NPT_NSTATE 56
+typedef struct ani_md_npt_params {
+  double dt, t_period, drag, p_period;
+  int mtchain, nc_tchain, mpchain, nc_pchain;
+} ani_md_npt_params;
+int ani_md_npt_init(double* npt_state, const double* lo3, const double* len3, int nlocal, void* stream);
+int ani_md_npt_chain(int phase, double* nh_state, double* npt_state, const double* work, int npart, const double* ev, double t_target,
+                     double p_target, double tdof, const ani_md_npt_params* params, void* stream);
+int ani_md_npt_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
+                                 const double* x_built, double* d2max, const double* nh_state, const double* npt_state,
+                                 double* shift, int nghost, void* stream);
+int ani_md_npt_final_integrate(double* v, const double* f, const double* dtfm, const double* mass, int nlocal,
+                               const double* npt_state, double* work, void* stream);
+int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,29 @@ def nh_state_dict(rec, mtchain: int = NH_MAXCHAIN) -> dict:
     return out
 
 
+# the barostat record of include/ani_md.h (ani_md_npt_*)
+NPT_NSTATE = 56
+NPT_STATE_KEYS = ("half_steps", "omega_dot", "omega", "press", "p_target", "W", "fv", "mu")
+
+
+class NptParams(C.Structure):
+    """ani_md_npt_params of include/ani_md.h"""
+    _fields_ = [("dt", C.c_double), ("t_period", C.c_double), ("drag", C.c_double), ("p_period", C.c_double), ("mtchain", C.c_int),
+                ("nc_tchain", C.c_int), ("mpchain", C.c_int), ("nc_pchain", C.c_int)]
+
+
+def npt_state_dict(rec, mpchain: int = NH_MAXCHAIN) -> dict:
+    """the ANI_MD_NPT_NSTATE doubles of a barostat record (host array) as a dict; eta, eta_dot, eta_dotdot: the first mpchain links
+    of the barostat chain"""
+    rec = np.asarray(rec, dtype=np.float64)
+    out = dict(zip(NPT_STATE_KEYS, rec[:8].tolist()))
+    out.update(lo=rec[8:11].copy(), len=rec[11:14].copy(), ratio=rec[14:17].copy(), c=rec[17:20].copy(), v0=float(rec[20]),
+               ecouple=float(rec[21]), nonfinite=float(rec[22]), natoms=float(rec[23]), ecouple_chain=float(rec[48]), vol=float(rec[49]))
+    for k, name in enumerate(("eta", "eta_dot", "eta_dotdot")):
+        out[name] = rec[24 + 8 * k: 24 + 8 * k + mpchain].copy()
+    return out
+
+
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
     """ani_md_fire_params with the defaults of LAMMPS `min_modify` (dtmax = 10 dt0, dtmin = 0.02 dt0, ...); kw overrides them"""
     vals = dict(dt0=float(dt0), dtmax=10.0 * dt0, dtmin=0.02 * dt0, dtgrow=1.1, dtshrink=0.5, alpha0=0.25, alphashrink=0.99,
@@ -206,6 +229,14 @@ def lib():
         L.ani_md_thermo_work_size.argtypes = [C.c_int]
         L.ani_md_thermo.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_npt_init.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ani_md_npt_chain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                       C.c_double, C.POINTER(NptParams), C.c_void_p]
+        L.ani_md_npt_initial_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ani_md_npt_final_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        L.ani_md_npt_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

@@ -150,22 +150,39 @@ class DomainComm:
         self.device = device
         self.cut = float(cutghost)
         self.periodic = tuple(bool(v) for v in periodic)
-        self.lo_np = np.asarray(box_lo, dtype=np.float64)
-        self.len_np = np.asarray(box_len, dtype=np.float64)
-        self.box_lo = torch.as_tensor(self.lo_np, device=device)
-        self.box_len = torch.as_tensor(self.len_np, device=device)
         self.host_staged = (native is None and self.world > 1 and dist.get_backend(group) == "gloo" and
                             torch.device(device).type == "cuda")
         r = self.rank
         self.me = (r % px, (r // px) % py, r // (px * py))   # harness/lmp_harness.cpp: rank = ix + px*(iy + py*iz)
+        self.set_box(box_lo, box_len)
+        self.nlocal = 0
+        self.nghost = 0
+        self.send_idx = torch.zeros(0, dtype=torch.long, device=device)
+        self.send_shift = torch.zeros((0, 3), dtype=torch.float64, device=device)
+        self.send_splits = [0] * self.world
+        self.recv_splits = [0] * self.world
+
+    def set_box(self, box_lo, box_len):
+        """The geometry that depends on the box: this rank's brick and the table of (brick, image shift) combinations of the ghost
+        shell.  Called by the constructor, and again by a caller whose box has changed (VerletRun under a barostat, before it
+        re-neighbours): the image count per dimension nimg = ceil(cut / len) can change, and with it the number of combinations.
+        The ghost set of the last `borders` is not touched."""
+        px, py, pz = self.grid
+        device = self.device
+        self.lo_np = np.asarray(box_lo, dtype=np.float64)
+        self.len_np = np.asarray(box_len, dtype=np.float64)
+        self.box_lo = torch.as_tensor(self.lo_np, device=device)
+        self.box_len = torch.as_tensor(self.len_np, device=device)
         P = np.array(self.grid, dtype=np.float64)
         self.sub_lo = self.lo_np + self.len_np * np.array(self.me) / P
         self.sub_hi = self.lo_np + self.len_np * (np.array(self.me) + 1) / P
         # per dimension: the (brick, image shift) combinations whose widened brick can contain an image of an atom owned
         # here; [lo, hi) is the interval of the UNSHIFTED coordinate that qualifies
         combos = []
+        self.nimg_max = 0   # the largest image count of the shell
         for d in range(3):
             nimg = int(np.ceil(self.cut / self.len_np[d])) if self.periodic[d] else 0
+            self.nimg_max = max(self.nimg_max, nimg)
             cd = []
             for b in range(self.grid[d]):
                 blo = self.lo_np[d] + self.len_np[d] * b / self.grid[d]
@@ -191,12 +208,6 @@ class DomainComm:
                                  device=device).reshape(-1, 1, 3)
         self._chi = torch.tensor([[combos[d][t[1 + d]][3] for d in range(3)] for t in full], dtype=torch.float64,
                                  device=device).reshape(-1, 1, 3)
-        self.nlocal = 0
-        self.nghost = 0
-        self.send_idx = torch.zeros(0, dtype=torch.long, device=device)
-        self.send_shift = torch.zeros((0, 3), dtype=torch.float64, device=device)
-        self.send_splits = [0] * self.world
-        self.recv_splits = [0] * self.world
 
     # ---- plumbing -----------------------------------------------------------------------------------------------
     def _counts(self, send_counts):

@@ -695,43 +695,33 @@ __global__ __launch_bounds__(256) void nh_kinetic_kernel(const double* __restric
   if (threadIdx.x == 0) part[blockIdx.x] = k2;
 }
 
-__global__ __launch_bounds__(256) void nh_chain_kernel(double* __restrict__ state, const double* __restrict__ part, int npart,
-                                                       double t_target, double tdof, double kt, double ket,
-                                                       ani_md_nh_params p) {
-  __shared__ double red[4];
-  double K2 = 0.0;
-  for (int b = threadIdx.x; b < npart; b += 256) K2 += part[b];
-  K2 = block_sum_fixed(K2, red);
-  if (threadIdx.x != 0) return;
-  if (npart == 0) K2 = state[NS_K2];
-  state[NS_TTARGET] = t_target;
-  state[NS_TDOF] = tdof;
-  state[NS_ZERO] = 0.0;
-  if (!finite_d(K2)) {
-    state[NS_K2] = K2;
-    state[NS_S] = 1.0;
-    state[NS_NONFINITE] += 1.0;
-    return;
-  }
-  const int M = p.mtchain;
-  double eta[ANI_MD_NH_MAXCHAIN], ed[ANI_MD_NH_MAXCHAIN + 1], edd[ANI_MD_NH_MAXCHAIN], Q[ANI_MD_NH_MAXCHAIN];
-  // kt = k_B t_target and ket = tdof kt come rounded from the host: formed here, K2 - tdof kt would contract into one
-  // multiply-add and a chain at rest exactly on target would start to move
-  const double tf = 1.0 / p.t_period;
+// The chain's half-step of include/ani_md.h on one thread: K2 is scaled in place, s and ecouple come back, eta / ed / edd are the
+// chain's links in registers (chain_load / the caller's stores).  The thermostat chain and the barostat chain are this one function.
+// kt = k_B t_target and ket = tdof kt come rounded from the host: formed here, K2 - tdof kt would contract into one multiply-add
+// and a chain at rest exactly on target would start to move.
+__device__ __forceinline__ void chain_load(const double* __restrict__ links, int M, double (&eta)[ANI_MD_NH_MAXCHAIN],
+                                           double (&ed)[ANI_MD_NH_MAXCHAIN + 1], double (&edd)[ANI_MD_NH_MAXCHAIN]) {
 #pragma unroll
   for (int k = 0; k < ANI_MD_NH_MAXCHAIN; k++) {
     const bool used = k < M;
-    eta[k] = used ? state[NS_ETA + k] : 0.0;
-    ed[k] = used ? state[NS_ETADOT + k] : 0.0;
-    edd[k] = used ? state[NS_ETADOTDOT + k] : 0.0;
-    Q[k] = (k == 0 ? ket : kt) / (tf * tf);
+    eta[k] = used ? links[k] : 0.0;
+    ed[k] = used ? links[ANI_MD_NH_MAXCHAIN + k] : 0.0;
+    edd[k] = used ? links[2 * ANI_MD_NH_MAXCHAIN + k] : 0.0;
   }
   ed[ANI_MD_NH_MAXCHAIN] = 0.0;
-  const double nf = 1.0 / (double)p.nc_tchain, dfac = 1.0 - p.dt * p.drag / (double)p.nc_tchain;
-  const double h2 = nf * p.dt / 2.0, h4 = nf * p.dt / 4.0, h8 = nf * p.dt / 8.0;
+}
+__device__ __forceinline__ void chain_half_step(double& K2, double kt, double ket, double t_period, double drag, double dt, int M,
+                                                int nc, double (&eta)[ANI_MD_NH_MAXCHAIN], double (&ed)[ANI_MD_NH_MAXCHAIN + 1],
+                                                double (&edd)[ANI_MD_NH_MAXCHAIN], double& s_out, double& ec_out) {
+  double Q[ANI_MD_NH_MAXCHAIN];
+  const double tf = 1.0 / t_period;
+#pragma unroll
+  for (int k = 0; k < ANI_MD_NH_MAXCHAIN; k++) Q[k] = (k == 0 ? ket : kt) / (tf * tf);
+  const double nf = 1.0 / (double)nc, dfac = 1.0 - dt * drag / (double)nc;
+  const double h2 = nf * dt / 2.0, h4 = nf * dt / 4.0, h8 = nf * dt / 8.0;
   edd[0] = (K2 - ket) / Q[0];
   double s = 1.0;
-  for (int it = 0; it < p.nc_tchain; it++) {
+  for (int it = 0; it < nc; it++) {
     for (int k = M - 1; k >= 1; k--) {
       const double e = exp(-h8 * ed[k + 1]);
       ed[k] = ((ed[k] * e + edd[k] * h4) * dfac) * e;
@@ -753,6 +743,32 @@ __global__ __launch_bounds__(256) void nh_chain_kernel(double* __restrict__ stat
   }
   double ec = ket * eta[0] + 0.5 * Q[0] * ed[0] * ed[0];
   for (int k = 1; k < M; k++) ec += kt * eta[k] + 0.5 * Q[k] * ed[k] * ed[k];
+  s_out = s;
+  ec_out = ec;
+}
+
+__global__ __launch_bounds__(256) void nh_chain_kernel(double* __restrict__ state, const double* __restrict__ part, int npart,
+                                                       double t_target, double tdof, double kt, double ket,
+                                                       ani_md_nh_params p) {
+  __shared__ double red[4];
+  double K2 = 0.0;
+  for (int b = threadIdx.x; b < npart; b += 256) K2 += part[b];
+  K2 = block_sum_fixed(K2, red);
+  if (threadIdx.x != 0) return;
+  if (npart == 0) K2 = state[NS_K2];
+  state[NS_TTARGET] = t_target;
+  state[NS_TDOF] = tdof;
+  state[NS_ZERO] = 0.0;
+  if (!finite_d(K2)) {
+    state[NS_K2] = K2;
+    state[NS_S] = 1.0;
+    state[NS_NONFINITE] += 1.0;
+    return;
+  }
+  double eta[ANI_MD_NH_MAXCHAIN], ed[ANI_MD_NH_MAXCHAIN + 1], edd[ANI_MD_NH_MAXCHAIN];
+  chain_load(state + NS_ETA, p.mtchain, eta, ed, edd);
+  double s, ec;
+  chain_half_step(K2, kt, ket, p.t_period, p.drag, p.dt, p.mtchain, p.nc_tchain, eta, ed, edd, s, ec);
   state[NS_COUNT] += 1.0;
   state[NS_K2] = K2;
   state[NS_S] = s;
@@ -813,6 +829,188 @@ __global__ __launch_bounds__(256) void nh_final_integrate_kernel(double* __restr
   }
   k2 = block_sum_fixed(k2, red);
   if (threadIdx.x == 0) part[blockIdx.x] = k2;
+}
+
+// ---- isotropic barostat (include/ani_md.h, ani_md_npt_*) --------------------------------------------------------------------
+// The box is six doubles of the barostat record; one thread of one workgroup moves it, the per-atom kernels read mu, fv, c and the
+// shift ratio from the record.  Everything a half-step decides is formed in registers first and written only when K2, Wtr and the
+// new strain rate are finite.
+enum { PS_COUNT = 0, PS_WD, PS_OMEGA, PS_P, PS_PTARGET, PS_W, PS_FV, PS_MU, PS_LO = 8, PS_LEN = 11, PS_RATIO = 14, PS_C = 17, PS_V0 = 20,
+       PS_ECOUPLE, PS_NONFINITE, PS_NATOMS, PS_ETA = 24, PS_ETADOT = 32, PS_ETADOTDOT = 40, PS_ECHAIN = 48, PS_VOL, PS_N = 56 };
+static_assert(PS_N == ANI_MD_NPT_NSTATE && PS_ETADOT - PS_ETA == ANI_MD_NH_MAXCHAIN && PS_ETADOTDOT - PS_ETADOT == ANI_MD_NH_MAXCHAIN,
+              "barostat record layout of include/ani_md.h");
+
+__global__ void npt_init_kernel(double* __restrict__ ps, double lo0, double lo1, double lo2, double l0, double l1, double l2, double n) {
+  for (int k = 0; k < PS_N; k++) ps[k] = 0.0;
+  const double lo[3] = {lo0, lo1, lo2}, len[3] = {l0, l1, l2};
+  for (int k = 0; k < 3; k++) {
+    ps[PS_LO + k] = lo[k];
+    ps[PS_LEN + k] = len[k];
+    ps[PS_RATIO + k] = 1.0;
+    ps[PS_C + k] = lo[k] + 0.5 * len[k];
+  }
+  const double V = (l0 * l1) * l2;
+  ps[PS_FV] = 1.0;
+  ps[PS_MU] = 1.0;
+  ps[PS_V0] = V;
+  ps[PS_VOL] = V;
+  ps[PS_NATOMS] = n;
+}
+
+__global__ __launch_bounds__(256) void npt_chain_kernel(int phase, double* __restrict__ ns, double* __restrict__ ps,
+                                                        const double* __restrict__ part, int npart, const double* __restrict__ ev,
+                                                        double t_target, double p_target, double tdof, double kt, double ket,
+                                                        ani_md_npt_params p) {
+  __shared__ double red[4];
+  double K2 = 0.0;
+  for (int b = threadIdx.x; b < npart; b += 256) K2 += part[b];
+  K2 = block_sum_fixed(K2, red);
+  if (threadIdx.x != 0) return;
+  if (npart == 0) K2 = ns[NS_K2];
+  const double K2_in = K2;
+  const double Wtr = (ev[1] + ev[5]) + ev[9];
+  const double N = ps[PS_NATOMS];
+  const double W = ((N + 1.0) * kt) * (p.p_period * p.p_period);
+  double lo[3], len[3], c[3];
+  for (int k = 0; k < 3; k++) { lo[k] = ps[PS_LO + k]; len[k] = ps[PS_LEN + k]; c[k] = ps[PS_C + k]; }
+  const double V = (len[0] * len[1]) * len[2];
+  double wd = ps[PS_WD];
+  double eta[ANI_MD_NH_MAXCHAIN], ed[ANI_MD_NH_MAXCHAIN + 1], edd[ANI_MD_NH_MAXCHAIN];
+  double peta[ANI_MD_NH_MAXCHAIN], ped[ANI_MD_NH_MAXCHAIN + 1], pedd[ANI_MD_NH_MAXCHAIN];
+  chain_load(ns + NS_ETA, p.mtchain, eta, ed, edd);
+  chain_load(ps + PS_ETA, p.mpchain, peta, ped, pedd);
+  double s = 1.0, ec = 0.0, sb = 1.0, ecb = 0.0, P = 0.0;
+  const double hdt = 0.5 * p.dt;
+  if (phase == 0) {
+    double Kb = (W * wd) * wd;
+    chain_half_step(Kb, kt, kt, p.p_period, 0.0, p.dt, p.mpchain, p.nc_pchain, peta, ped, pedd, sb, ecb);
+    wd *= sb;
+    chain_half_step(K2, kt, ket, p.t_period, p.drag, p.dt, p.mtchain, p.nc_tchain, eta, ed, edd, s, ec);
+  }
+  {
+    P = (K2 + Wtr) / (3.0 * V) * NH_NKTV2P;
+    const double a = (P - p_target) * V / NH_NKTV2P, b = K2 / (3.0 * N);
+    wd += hdt * ((a + b) / W);
+  }
+  if (phase != 0) {
+    chain_half_step(K2, kt, ket, p.t_period, p.drag, p.dt, p.mtchain, p.nc_tchain, eta, ed, edd, s, ec);
+    double Kb = (W * wd) * wd;
+    chain_half_step(Kb, kt, kt, p.p_period, 0.0, p.dt, p.mpchain, p.nc_pchain, peta, ped, pedd, sb, ecb);
+    wd *= sb;
+  }
+  ns[NS_TTARGET] = t_target;
+  ns[NS_TDOF] = tdof;
+  ns[NS_ZERO] = 0.0;
+  ps[PS_PTARGET] = p_target;
+  if (!(finite_d(K2_in) && finite_d(Wtr) && finite_d(wd))) {
+    ns[NS_K2] = K2_in;
+    ns[NS_S] = 1.0;
+    ns[NS_NONFINITE] += 1.0;
+    ps[PS_FV] = 1.0;
+    ps[PS_MU] = 1.0;
+    for (int k = 0; k < 3; k++) ps[PS_RATIO + k] = 1.0;
+    ps[PS_NONFINITE] += 1.0;
+    return;
+  }
+  double Vnew = V;
+  if (phase == 0) {
+    const double fv = exp(-hdt * (wd * (1.0 + 1.0 / N))), mu = exp(hdt * wd), mu2 = mu * mu;
+    ps[PS_FV] = fv;
+    ps[PS_MU] = mu;
+    double ln[3];
+    for (int k = 0; k < 3; k++) {
+      ln[k] = len[k] * mu2;
+      const double d = lo[k] - c[k];
+      ps[PS_LO + k] = c[k] + mu2 * d;
+      ps[PS_LEN + k] = ln[k];
+      ps[PS_RATIO + k] = ln[k] / len[k];
+    }
+    Vnew = (ln[0] * ln[1]) * ln[2];
+    ps[PS_OMEGA] += p.dt * wd;
+  }
+  ns[NS_COUNT] += 1.0;
+  ns[NS_K2] = K2;
+  ns[NS_S] = s;
+  ns[NS_ECOUPLE] = ec;
+  ps[PS_COUNT] += 1.0;
+  ps[PS_WD] = wd;
+  ps[PS_P] = P;
+  ps[PS_W] = W;
+  ps[PS_VOL] = Vnew;
+  ps[PS_ECHAIN] = ecb;
+  ps[PS_ECOUPLE] = 3.0 * (0.5 * W * wd * wd + ecb) + p_target * (Vnew - ps[PS_V0]) / NH_NKTV2P;
+#pragma unroll
+  for (int k = 0; k < ANI_MD_NH_MAXCHAIN; k++) {
+    ns[NS_ETA + k] = eta[k];
+    ns[NS_ETADOT + k] = ed[k];
+    ns[NS_ETADOTDOT + k] = edd[k];
+    ps[PS_ETA + k] = peta[k];
+    ps[PS_ETADOT + k] = ped[k];
+    ps[PS_ETADOTDOT + k] = pedd[k];
+  }
+}
+
+// step 5 of the first half on the owned rows, step 7 on the shift rows behind them: one grid over n + nghost rows
+__global__ __launch_bounds__(256) void npt_initial_integrate_kernel(double* __restrict__ x, double* __restrict__ v,
+                                                                    const double* __restrict__ f, const double* __restrict__ dtfm,
+                                                                    double dt, int n, const double* __restrict__ xb,
+                                                                    double* __restrict__ d2max, const double* __restrict__ ns,
+                                                                    const double* __restrict__ ps, double* __restrict__ shift,
+                                                                    int nghost) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double d2 = 0.0;
+  if (i < n) {
+    const double s = dtfm[i], sc = ns[NS_S] * ps[PS_FV], mu = ps[PS_MU];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const size_t e = 3 * (size_t)i + k;
+      const double c = ps[PS_C + k];
+      const double vk = sc * v[e] + s * f[e];
+      double xk = c + mu * (x[e] - c);
+      xk = xk + dt * vk;
+      xk = c + mu * (xk - c);
+      v[e] = vk;
+      x[e] = xk;
+      const double d = xk - xb[e];
+      d2 += d * d;
+    }
+  } else if (i - n < nghost) {
+    const size_t g = 3 * (size_t)(i - n);
+#pragma unroll
+    for (int k = 0; k < 3; k++) shift[g + k] *= ps[PS_RATIO + k];
+  }
+  __shared__ double red[4];
+  d2 = block_max(d2, red);
+  if (threadIdx.x == 0 && blockIdx.x * blockDim.x < n) raise_d2max(d2, d2max);
+}
+
+// nh_final_integrate_kernel with v *= fv behind the kick; the partials are nh_kinetic_kernel's on what it wrote
+__global__ __launch_bounds__(256) void npt_final_integrate_kernel(double* __restrict__ v, const double* __restrict__ f,
+                                                                  const double* __restrict__ dtfm, const double* __restrict__ mass,
+                                                                  int n, const double* __restrict__ ps, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double k2 = 0.0;
+  if (i < n) {
+    const double s = dtfm[i], fv = ps[PS_FV];
+    double vn[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      vn[k] = (v[3 * (size_t)i + k] + s * f[3 * (size_t)i + k]) * fv;
+      v[3 * (size_t)i + k] = vn[k];
+    }
+    k2 = k2_term(mass[i], vn[0], vn[1], vn[2]);
+  }
+  k2 = block_sum_fixed(k2, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = k2;
+}
+
+__global__ void npt_check_kernel(double* __restrict__ d2max, const double* __restrict__ ev, const double* __restrict__ ps,
+                                 double* __restrict__ out) {
+  const double e = ev[0];
+  out[0] = finite_d(e) ? d2max[0] : __longlong_as_double(0x7ff0000000000000LL);
+  d2max[0] = 0.0;
+  for (int k = 0; k < PS_N; k++) out[1 + k] = ps[k];
 }
 
 // part[c nblk + b] = K_c of block b, c = xx, yy, zz, xy, xz, yz
@@ -1058,6 +1256,48 @@ int ani_md_nh_final_integrate(double* v, const double* f, const double* dtfm, co
   if (nlocal <= 0) return 0;
   if (!mass || !work) return (int)hipErrorInvalidValue;
   return launch(nh_final_integrate_kernel, blocks(nlocal), 256, stream, v, f, dtfm, mass, nlocal, work);
+}
+
+int ani_md_npt_init(double* npt_state, const double* lo3, const double* len3, int nlocal, void* stream) {
+  if (!npt_state || !lo3 || !len3 || nlocal <= 0) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < 3; k++)
+    if (!(len3[k] > 0.0) || !(len3[k] - len3[k] == 0.0) || !(lo3[k] - lo3[k] == 0.0)) return (int)hipErrorInvalidValue;
+  return launch(npt_init_kernel, dim3(1), 1, stream, npt_state, lo3[0], lo3[1], lo3[2], len3[0], len3[1], len3[2], (double)nlocal);
+}
+
+int ani_md_npt_chain(int phase, double* nh_state, double* npt_state, const double* work, int npart, const double* ev, double t_target,
+                     double p_target, double tdof, const ani_md_npt_params* params, void* stream) {
+  if (!nh_state || !npt_state || !ev || !params || npart < 0 || (npart > 0 && !work) || (phase != 0 && phase != 1))
+    return (int)hipErrorInvalidValue;
+  const ani_md_npt_params& q = *params;
+  if (q.mtchain < 1 || q.mtchain > ANI_MD_NH_MAXCHAIN || q.mpchain < 1 || q.mpchain > ANI_MD_NH_MAXCHAIN || q.nc_tchain < 1 ||
+      q.nc_pchain < 1 || !(q.t_period > 0.0) || !(q.p_period > 0.0) || !(q.dt > 0.0) || !(t_target > 0.0) || !(tdof > 0.0) ||
+      !(p_target - p_target == 0.0))
+    return (int)hipErrorInvalidValue;
+  const double kt = 0.0019872067 * t_target, ket = tdof * kt;
+  return launch(npt_chain_kernel, dim3(1), 256, stream, phase, nh_state, npt_state, work, npart, ev, t_target, p_target, tdof, kt, ket, q);
+}
+
+int ani_md_npt_initial_integrate(double* x, double* v, const double* f, const double* dtfm, double dt, int nlocal,
+                                 const double* x_built, double* d2max, const double* nh_state, const double* npt_state,
+                                 double* shift, int nghost, void* stream) {
+  if (nghost < 0) return (int)hipErrorInvalidValue;
+  if (nlocal <= 0) return 0;
+  if (!nh_state || !npt_state || (nghost > 0 && !shift)) return (int)hipErrorInvalidValue;
+  return launch(npt_initial_integrate_kernel, blocks(nlocal + nghost), 256, stream, x, v, f, dtfm, dt, nlocal, x_built, d2max, nh_state,
+                npt_state, shift, nghost);
+}
+
+int ani_md_npt_final_integrate(double* v, const double* f, const double* dtfm, const double* mass, int nlocal,
+                               const double* npt_state, double* work, void* stream) {
+  if (nlocal <= 0) return 0;
+  if (!mass || !work || !npt_state) return (int)hipErrorInvalidValue;
+  return launch(npt_final_integrate_kernel, blocks(nlocal), 256, stream, v, f, dtfm, mass, nlocal, npt_state, work);
+}
+
+int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, double* out, void* stream) {
+  if (!npt_state) return (int)hipErrorInvalidValue;
+  return launch(npt_check_kernel, dim3(1), 1, stream, d2max, ev, npt_state, out);
 }
 
 int ani_md_thermo_work_size(int nlocal) { return 6 * nblocks(nlocal); }

@@ -82,6 +82,19 @@ def constraint_clusters(bonds, tags):
     return cl, slot_bond
 
 
+def npt_rebuild_limit(skin, lo_built, len_built, lo_now, len_now, nimg_max) -> float:
+    """The squared displacement of an owned atom since the build above which a loop whose box moves re-neighbours:
+    max(0, (skin - nimg_max (d_lo + d_hi)) / 2)^2, with d_lo and d_hi the Euclidean displacements of the two box corners since the
+    build and nimg_max the largest image count of the ghost shell.  A pair's distance changes by at most the two owners'
+    displacements plus the change of the image shift between them; the displacements are taken against the unscaled positions of
+    the build, so they include the dilation, and a shift of up to nimg_max box lengths changes by at most nimg_max (d_lo + d_hi).
+    With one image this is Neighbor::check_distance with `boxcheck`; with a box at rest it is the constant (skin / 2)^2."""
+    lo_b, len_b, lo_n, len_n = (np.asarray(a, dtype=np.float64) for a in (lo_built, len_built, lo_now, len_now))
+    d_lo = float(np.sqrt(((lo_n - lo_b) ** 2).sum()))
+    d_hi = float(np.sqrt(((lo_n + len_n - lo_b - len_b) ** 2).sum()))
+    return max(0.0, 0.5 * (skin - nimg_max * (d_lo + d_hi))) ** 2
+
+
 class VerletRun:
     def __init__(self, ani, inp, box_len, device, dt: float = 0.5, cutoff: float = 5.1, skin: float = 2.0,
                  ghost_margin: float = 0.0, every: int = 10, masses=ANI2X_MASSES, group=None, seed: int = 12345,
@@ -155,6 +168,7 @@ class VerletRun:
         self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
         self._rdf_every = 0    # radial distribution functions (set_rdf): 0 = none, else a frame every so many steps
         self._nvt = None       # Nose-Hoover chain (set_nvt): None, or the device record, scratch and parameters
+        self._npt = None       # isotropic barostat (set_npt): None, or the device record, its check buffers, parameters and targets
         self._thermo_buf = None
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
@@ -232,17 +246,13 @@ class VerletRun:
             self._xbuilt_buf = torch.empty((n, 3), dtype=torch.float64, device=self.device)
             self._chk_dev = torch.zeros(1, dtype=torch.float64, device=self.device)
             self._chk_host = torch.zeros(1, dtype=torch.float64).pin_memory()
-            self._clo2 = dc._clo.reshape(-1, 3).contiguous()
-            self._chi2 = dc._chi.reshape(-1, 3).contiguous()
-            self._cshift2 = dc._shift.reshape(-1, 3).contiguous()
-            self._ncombo = int(self._clo2.shape[0])
-            nblk = max((n + 255) // 256, 1)
-            self._blk = torch.empty(2 * max(self._ncombo, 1) * nblk, dtype=torch.int32, device=self.device)
-            self._cnt_dev = torch.zeros(self._ncombo + 1, dtype=torch.int32, device=self.device)
-            self._cnt_host = torch.zeros(self._ncombo + 1, dtype=torch.int32).pin_memory()
-            self._lo3 = np.ascontiguousarray(self._box_lo_np, dtype=np.float64)
-            self._len3 = np.ascontiguousarray(self._box_len_np, dtype=np.float64)
+            self._ncombo = -1
+            self._shell_tables()
+            self._lo3 = np.array(self._box_lo_np, dtype=np.float64)
+            self._len3 = np.array(self._box_len_np, dtype=np.float64)
             self._pmask = sum(1 << k for k in range(3) if dc.periodic[k])
+        if self._npt is not None and not self._npt["fresh"]:
+            self._npt_read_box()      # a rebuild that no look of the host precedes: one read of the record
         x = self._xbuf
         self._check(md.ani_md_wrap_positions(x.data_ptr(), n, self._lo3.ctypes.data, self._len3.ctypes.data, self._pmask, st))
         ng = 0
@@ -278,8 +288,38 @@ class VerletRun:
         self._xbuilt_buf.copy_(self.x[:n])
         self.x_built = self._xbuilt_buf
         self._check(md.ani_md_check(self._d2max.data_ptr(), self.ev.data_ptr(), self._chk_dev.data_ptr(), st))   # zeroes the maximum
+        if self._npt is not None:     # the box this list belongs to: what the re-neighbouring limit measures from
+            self._npt.update(lo_built=self._box_lo_np.copy(), len_built=self._box_len_np.copy(), nimg_max=dc.nimg_max)
         self.since_build = 0
         self.nbuilds += 1
+
+    def _shell_tables(self):
+        """the ghost shell's combination table of the DomainComm as the [ncombo, 3] arrays of the shell kernels, and their count
+        buffers: made at the first build, and again whenever the box has changed (the number of combinations can change with it)"""
+        dc, n = self.dc, self.nlocal
+        self._clo2 = dc._clo.reshape(-1, 3).contiguous()
+        self._chi2 = dc._chi.reshape(-1, 3).contiguous()
+        self._cshift2 = dc._shift.reshape(-1, 3).contiguous()
+        ncombo = int(self._clo2.shape[0])
+        if ncombo != self._ncombo:
+            self._ncombo = ncombo
+            nblk = max((n + 255) // 256, 1)
+            self._blk = torch.empty(2 * max(ncombo, 1) * nblk, dtype=torch.int32, device=self.device)
+            self._cnt_dev = torch.zeros(ncombo + 1, dtype=torch.int32, device=self.device)
+            self._cnt_host = torch.zeros(ncombo + 1, dtype=torch.int32).pin_memory()
+
+    def _set_box(self, lo, length):
+        """The host's copy of a box that the device has moved: the loop's own arrays, the DomainComm geometry with its combination
+        table, and the shell kernels' tables.  Raises for a box that is not finite or not positive."""
+        lo, length = np.array(lo, dtype=np.float64), np.array(length, dtype=np.float64)
+        if not (np.isfinite(lo).all() and np.isfinite(length).all() and (length > 0.0).all()):
+            raise RuntimeError(f"the barostat's box is not finite or not positive: lo {lo.tolist()}, len {length.tolist()}")
+        if (lo == self._box_lo_np).all() and (length == self._box_len_np).all():
+            return
+        self._box_lo_np, self._box_len_np = lo, length
+        self._lo3[:], self._len3[:] = lo, length
+        self.dc.set_box(lo, length)
+        self._shell_tables()
 
     def _build_list(self):
         """Domain::pbc + Comm::exchange + Comm::borders + Neighbor::build."""
@@ -361,11 +401,21 @@ class VerletRun:
         self.v *= (T / t_now) ** 0.5
 
     # ---- the schedule of a step: first half, middle, second half ---------------------------------------
-    def _first_half(self, t_target=None, npart: int = 0):
+    def _first_half(self, t_target=None, npart: int = 0, p_target=None):
         """fix nve / fix nvt initial_integrate: v += dtf f / m ; x += dt v  (fused: + the displacement maximum of check_distance),
-        behind the chain's half-step with a thermostat (v = s v first); then the position stage of the constraints"""
+        behind the chain's half-step with a thermostat (v = s v first); with a barostat the chains' half-step that also moves the box
+        in its record, then the dilated move of the atoms and the scaling of the ghost shifts in one launch; then the position
+        stage of the constraints"""
         nvt = self._nvt
-        if nvt is not None:
+        if self._npt is not None:
+            self._npt_chain(0, t_target, p_target, npart)
+            self._npt["fresh"] = False     # the box moves: the host's copy is behind until it looks
+            self._check(self._md.ani_md_npt_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
+                                                              self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
+                                                              self._d2max.data_ptr(), nvt["state"].data_ptr(),
+                                                              self._npt["state"].data_ptr(), self._sshift.data_ptr(),
+                                                              self.ntotal - self.nlocal, self._stream))
+        elif nvt is not None:
             self._nvt_chain(t_target, npart)
             self._check(self._md.ani_md_nh_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
                                                              self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
@@ -385,17 +435,32 @@ class VerletRun:
         self.step_no += 1
         self.since_build += 1
         # Neighbor::decide + check_distance (every N steps, rebuild if any atom moved more than skin/2)
-        rebuild = bool(force_rebuild) or (self.since_build % self.every == 0 and self._look() > self._d2_rebuild)
+        rebuild = bool(force_rebuild) or (self.since_build % self.every == 0 and self._look() > self._rebuild_limit())
         self._ghosts_and_forces(rebuild)
         # on every path above the ghost rows of x are now the images of this step's owned positions
         if self._rdf_every and self.step_no % self._rdf_every == 0:
             self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
 
-    def _second_half(self, t_target=None):
+    def _rebuild_limit(self) -> float:
+        """what the worst squared displacement of a look is held against: (skin / 2)^2, or npt_rebuild_limit with the box of the
+        look (which has just refreshed the host's copy) against the box of the build"""
+        npt = self._npt
+        if npt is None:
+            return self._d2_rebuild
+        return npt_rebuild_limit(self.skin, npt["lo_built"], npt["len_built"], self._box_lo_np, self._box_len_np, npt["nimg_max"])
+
+    def _second_half(self, t_target=None, p_target=None):
         """fix langevin post_force + fix nve final_integrate and the velocity stage of the constraints; with a thermostat the
         pass that also leaves the partial sums of sum m v^2 (constrained: the plain one, the velocity stage, then the sums), the
         chain's half-step on them and the scaling (a uniform scale keeps r . (v_c - v_p) = 0)"""
         nvt = self._nvt
+        if self._npt is not None:
+            self._check(self._md.ani_md_npt_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(),
+                                                            nvt["mass"].data_ptr(), self.nlocal, self._npt["state"].data_ptr(),
+                                                            nvt["work"].data_ptr(), self._stream))
+            self._npt_chain(1, t_target, p_target, nvt["npart"])
+            self._check(self._md.ani_md_nh_scale(self.v.data_ptr(), self.nlocal, nvt["state"].data_ptr(), self._stream))
+            return
         if nvt is None or self._cons is not None:
             self._final_integrate()
             self.project_velocities()
@@ -408,21 +473,24 @@ class VerletRun:
             self._nvt_chain(t_target, nvt["npart"])
             self._check(self._md.ani_md_nh_scale(self.v.data_ptr(), self.nlocal, nvt["state"].data_ptr(), self._stream))
 
-    def _steps(self, nsteps: int, t_from=None, t_to=None, force_rebuild: bool = False, before_forces=None, after_forces=None):
+    def _steps(self, nsteps: int, t_from=None, t_to=None, force_rebuild: bool = False, before_forces=None, after_forces=None,
+               p_from=None, p_to=None):
         """nsteps steps of first half, middle, second half; with a thermostat the target goes from t_from (exclusive) to t_to (at
         the last step), and the call begins with the sum of the velocities as they are.  The one exception to the three pieces:
         where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints,
         the device loop -- the two are ONE launch, which carries the number of the step that ends."""
         nvt = self._nvt
         one_launch = self._fused and nvt is None and self._cons is None
-        t = None
+        t = p = None
         if nvt is not None:
             self._nvt_kinetic()
         for k in range(nsteps):
             if nvt is not None:
                 t = t_to if k + 1 == nsteps else t_from + ((k + 1) / nsteps) * (t_to - t_from)
+            if p_to is not None:
+                p = p_to if k + 1 == nsteps else p_from + ((k + 1) / nsteps) * (p_to - p_from)
             if k == 0 or not one_launch:
-                self._first_half(t, nvt["npart"] if nvt is not None and k == 0 else 0)   # later steps: the sum the chain scaled itself
+                self._first_half(t, nvt["npart"] if nvt is not None and k == 0 else 0, p)   # later steps: the sum the chain scaled itself
             if before_forces is not None:
                 before_forces(k)
             self._middle(force_rebuild)
@@ -435,14 +503,15 @@ class VerletRun:
                     1 if lang else 0, self._g1.data_ptr() if lang else None, self._g2.data_ptr() if lang else None,
                     self.tag.data_ptr(), self._seed, self.step_no, self.x_built.data_ptr(), self._d2max.data_ptr(), self._stream))
             else:
-                self._second_half(t)
+                self._second_half(t, p)
 
     def step(self, force_rebuild: bool = False):
         """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements).  With a thermostat
         (set_nvt) the step begins with a fresh kinetic sum and uses the current target: N calls agree with run(N) to the rounding of
         that sum, not bitwise."""
         t = self._nvt["t_target"] if self._nvt is not None else None
-        self._steps(1, t, t, force_rebuild)
+        p = self._npt["p_target"] if self._npt is not None else None
+        self._steps(1, t, t, force_rebuild, p_from=p, p_to=p)
 
     def run(self, nsteps: int, before_forces=None, after_forces=None):
         """``run N`` without per-step output: nothing looks at the full-step velocities between two steps, so the
@@ -457,9 +526,12 @@ class VerletRun:
             for _ in range(nsteps):
                 self.step()
             return
-        nvt = self._nvt
+        nvt, npt = self._nvt, self._npt
         if nvt is None:
             self._steps(int(nsteps), None, None, False, before_forces, after_forces)
+        elif npt is not None:
+            self._steps(int(nsteps), nvt["t_start"], nvt["t_stop"], False, before_forces, after_forces, npt["p_start"], npt["p_stop"])
+            nvt["t_target"], npt["p_target"] = nvt["t_stop"], npt["p_stop"]
         else:
             self._steps(int(nsteps), nvt["t_start"], nvt["t_stop"], False, before_forces, after_forces)
             nvt["t_target"] = nvt["t_stop"]
@@ -475,8 +547,12 @@ class VerletRun:
         word: a scratch word in place of the loop's own maximum (warm_paths: nothing is zeroed that the loop needs, nothing is
         judged)."""
         d2max = self._d2max if word is None else word
+        npt = self._npt if (extra is None and word is None) else None
         if self._native_rebuild:
-            if extra is None:
+            if npt is not None:   # the barostat record behind the word: the same read brings the box of this moment
+                dev, host = npt["chk_dev"], npt["chk_host"]
+                self._check(self._md.ani_md_npt_check(d2max.data_ptr(), self.ev.data_ptr(), npt["state"].data_ptr(), dev.data_ptr(), self._stream))
+            elif extra is None:
                 dev, host = self._chk_dev, self._chk_host
                 self._check(self._md.ani_md_check(d2max.data_ptr(), self.ev.data_ptr(), dev.data_ptr(), self._stream))
             else:
@@ -499,6 +575,10 @@ class VerletRun:
         if worst == float("inf"):
             raise RuntimeError("non-finite energy from the device step: a neighbour count exceeded the kernels' LDS "
                                "capacity (ANI_ERR_CAPACITY) or the forces diverged")
+        if npt is not None:
+            rec = npt["chk_host"][1:].numpy()
+            self._set_box(rec[8:11], rec[11:14])
+            npt["fresh"] = True
         if self._cons is not None and self._native_rebuild:
             self._constraint_health(self._chk_host[1:])
         return worst
@@ -658,6 +738,7 @@ class VerletRun:
         (t_stop - t_start) in both of its half-steps, every run() ramps anew, afterwards the target stays at t_stop; step() uses the
         current target (t_start before the first run()).  The target is a kernel argument: the host reads nothing.
         Raises with ``langevin``, with several ranks, for a temperature that is not positive and for mtchain outside 1..8."""
+        self._clear_npt()             # set_nvt and set_npt clear each other
         if t_start is None:
             self._nvt = None
             return
@@ -704,6 +785,105 @@ class VerletRun:
         from .ani_hip import nh_state_dict
         return nh_state_dict(self._nvt["state"].cpu().numpy(), self._nvt["mtchain"])
 
+    # ---- isotropic barostat ----------------------------------------------------------------------------------
+    def set_npt(self, t_start, t_stop=None, t_period=None, p_start: float = 1.0, p_stop=None, p_period=None, mtchain: int = 3,
+                mpchain: int = 3, nc_tchain: int = 1, nc_pchain: int = 1, drag: float = 0.0):
+        """``fix npt temp t_start t_stop t_period iso p_start p_stop p_period``: the isotropic Martyna-Tobias-Klein barostat with a
+        chain of `mpchain` links on top of the Nose-Hoover thermostat chain of set_nvt, on the device (ani_md_npt_*,
+        include/ani_md.h; `mtk yes`), fp64 whatever the handle.  Pressures in atm; p_stop None: p_start; p_period in fs, None:
+        1000 dt; the temperature arguments, nc_tchain and drag as set_nvt.  drag is the thermostat's only: the barostat and its chain
+        have none (LAMMPS applies ``fix_modify drag`` to both).  set_npt(None) clears barostat and thermostat: the loop launches what
+        it launched before, in the box as it is then.  set_npt and set_nvt clear each other.  Both chains start at rest.
+        The box lives in the barostat's device record and changes in every step; a step launches what a thermostatted step launches
+        (chain, first half, second half, chain, scale) and never synchronises.  The host's copy of the box (box(), the DomainComm
+        geometry, the wrap's and the ghost shell's bounds) is refreshed by every look it takes anyway (the displacement check's
+        pinned read brings the record along) and before every re-neighbouring; a re-neighbouring wraps, selects the ghost shell,
+        bounds the list and sets the ghost shifts in the box of that moment, and between two of them the shifts are scaled with the
+        box.  The displacement check is held against npt_rebuild_limit.  The pressure ramps like the temperature: step k = 1..N of
+        run(N) has p_start + (k / N) (p_stop - p_start), afterwards the target stays at p_stop; step() uses the current target.
+        thermo() takes volume, ecouple (both chains, the strain rate's kinetic term and p_target (V - V0)) and density from the
+        record; minimize() leaves the barostat alone.
+        Raises without ``vflag`` (the barostat reads the pair virial of every step), with ``langevin``, with several ranks, without
+        native re-neighbouring, while constraints are set (the constraint virial is not accumulated and the constraint kernels take
+        the box from the host: the open lead), for temperatures or periods that are not positive, and for mtchain
+        or mpchain outside 1..8."""
+        if t_start is None:
+            self._clear_npt()
+            self._nvt = None
+            return
+        from . import ani_hip
+        if not self.vflag:
+            raise RuntimeError("VerletRun.set_npt needs vflag=True (the barostat reads the pair virial of every force evaluation)")
+        if self.langevin is not None:
+            raise RuntimeError("VerletRun.set_npt: the run has a Langevin thermostat (langevin=...); one temperature control at a time")
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.set_npt: one rank only (kinetic energy and virial are not reduced over ranks)")
+        if not self._native_rebuild:
+            raise RuntimeError("VerletRun.set_npt needs the device loop with native re-neighbouring (one rank on the GPU)")
+        if self._cons is not None:
+            raise RuntimeError("VerletRun.set_npt: bond constraints are set (the constraint virial is not accumulated and the "
+                               "constraint kernels take a host box) -- clear them with set_constraints([]) first")
+        p_start = float(p_start)
+        p_stop = p_start if p_stop is None else float(p_stop)
+        p_period = 1000.0 * self.dt if p_period is None else float(p_period)
+        if not (np.isfinite(p_start) and np.isfinite(p_stop)):
+            raise ValueError("VerletRun.set_npt: pressures must be finite")
+        if not (p_period > 0.0 and np.isfinite(p_period)) or int(nc_pchain) < 1:
+            raise ValueError("VerletRun.set_npt: p_period must be positive and nc_pchain >= 1")
+        if not 1 <= int(mpchain) <= ani_hip.NH_MAXCHAIN:
+            raise ValueError(f"VerletRun.set_npt: mpchain must be in 1..{ani_hip.NH_MAXCHAIN}")
+        self.set_nvt(t_start, t_stop, t_period, mtchain, nc_tchain, drag)     # the thermostat's record, scratch and refusals
+        nh = self._nvt["par"]
+        par = ani_hip.NptParams(self.dt, nh.t_period, nh.drag, p_period, nh.mtchain, nh.nc_tchain, int(mpchain), int(nc_pchain))
+        ns = ani_hip.NPT_NSTATE
+        state = torch.zeros(ns, dtype=torch.float64, device=self.device)
+        self._check(self._md.ani_md_npt_init(state.data_ptr(), self._lo3.ctypes.data, self._len3.ctypes.data, self.nlocal, self._stream))
+        self._npt = dict(p_start=p_start, p_stop=p_stop, p_target=p_start, par=par, state=state, mpchain=int(mpchain), fresh=True,
+                         chk_dev=torch.zeros(1 + ns, dtype=torch.float64, device=self.device),
+                         chk_host=torch.zeros(1 + ns, dtype=torch.float64).pin_memory(),
+                         lo_built=self._box_lo_np.copy(), len_built=self._box_len_np.copy(), nimg_max=self.dc.nimg_max)
+
+    def _clear_npt(self):
+        """the barostat goes: the host's copy of the box catches up first, the loop goes on in that box (re-neighboured in it, with
+        the forces evaluated again, when the box has moved since the last build)"""
+        npt = self._npt
+        if npt is not None:
+            if not npt["fresh"]:
+                self._npt_read_box()
+            self._npt = None
+            # the constant limit of a box at rest measures from the box of the build: a box that has moved since is re-neighboured now
+            if (self._box_lo_np != npt["lo_built"]).any() or (self._box_len_np != npt["len_built"]).any():
+                self._ghosts_and_forces(True)
+
+    def _npt_chain(self, phase: int, t_target: float, p_target: float, npart: int):
+        nvt, npt = self._nvt, self._npt
+        self._check(self._md.ani_md_npt_chain(phase, nvt["state"].data_ptr(), npt["state"].data_ptr(), nvt["work"].data_ptr(), npart,
+                                              self.ev.data_ptr(), t_target, p_target, 3.0 * self.nlocal - 3.0 - self._ncons,
+                                              npt["par"], self._stream))
+
+    def _npt_read_box(self):
+        """one synchronising read of the barostat record; the host's copy of the box follows it.  Returns the record."""
+        rec = self._npt["state"].cpu().numpy()
+        self._set_box(rec[8:11], rec[11:14])
+        self._npt["fresh"] = True
+        return rec
+
+    def npt_state(self) -> dict:
+        """the barostat's device record (one synchronising read): half_steps, omega_dot (the strain rate, 1/fs), omega (its time
+        integral: ln(L / L0)), press and p_target of the last strain-rate update (atm), W, fv, mu, lo, len, ratio (box and the shift
+        ratio of the last first half), c, v0, vol, ecouple (the barostat's part of the conserved quantity), ecouple_chain, nonfinite,
+        natoms, and eta, eta_dot, eta_dotdot of the mpchain links"""
+        if self._npt is None:
+            raise RuntimeError("VerletRun.npt_state: no barostat is set (set_npt)")
+        from .ani_hip import npt_state_dict
+        return npt_state_dict(self._npt_read_box(), self._npt["mpchain"])
+
+    def box(self):
+        """(lo [3], len [3]) of the periodic box as it is now; with a barostat one synchronising read of its record"""
+        if self._npt is not None:
+            self._npt_read_box()
+        return self._box_lo_np.copy(), self._box_len_np.copy()
+
     # ---- bond constraints ----------------------------------------------------------------------------------
     def set_constraints(self, bonds, lengths=None, tol: float = 1e-10, maxiter: int = 20, project: bool = True):
         """``fix shake`` / ``fix rattle`` on bonds: holonomic bond-length constraints in the RATTLE form (ani_md_shake_positions /
@@ -721,6 +901,9 @@ class VerletRun:
             raise RuntimeError("VerletRun.set_constraints: one rank only (a cluster's atoms would have to migrate together)")
         if not self._native_rebuild:
             raise RuntimeError("VerletRun.set_constraints needs the device loop with native re-neighbouring (one rank on the GPU)")
+        if self._npt is not None:
+            raise RuntimeError("VerletRun.set_constraints: a barostat is set (set_npt): the constraint virial is not accumulated and "
+                               "the constraint kernels take a host box")
         from . import ani_hip
         bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
         nb = int(bonds.shape[0])
@@ -896,7 +1079,8 @@ class VerletRun:
     def rdf(self, reset: bool = False) -> dict:
         """Read and normalise what was accumulated (ani_hip.rdf_normalise: r, g, coord), plus the raw counts [npair, nbins],
         centres [npair], frames, and pairs [npair, 2].  Species counts from the owned atoms, the volume from the box.  reset:
-        zero the accumulators afterwards."""
+        zero the accumulators afterwards.  With a barostat the volume is that of the box at the time of this read: LAMMPS'
+        ``compute rdf`` normalises every frame with the volume of its own moment, which is not built."""
         from .ani_hip import rdf_normalise
         cfg = self.ani.rdf_config()
         if cfg is None:
@@ -904,7 +1088,7 @@ class VerletRun:
         nbins, rmax, pairs = cfg
         counts, centres, frames = self.ani.rdf_read(reset=reset)
         n_of = np.bincount(self.species[: self.nlocal].cpu().numpy(), minlength=len(self.ani.species_symbols()))
-        out = rdf_normalise(counts, centres, nbins, rmax, pairs, n_of, float(np.prod(self._box_len_np)))
+        out = rdf_normalise(counts, centres, nbins, rmax, pairs, n_of, float(np.prod(self.box()[1])))
         out.update(counts=counts, centres=centres, frames=frames, pairs=pairs.copy())
         return out
 
@@ -926,7 +1110,8 @@ class VerletRun:
         """``thermo_style custom pe ke etotal temp press vol density`` from the device: one ani_md_thermo call (include/ani_md.h)
         and one read.  Keys: pe, ke, etotal (kcal/mol), temp (K, on 3 N - 3 - nb degrees of freedom), press and pxx pyy pzz pxy pxz
         pyz (atm: kinetic tensor plus the pair virial of the last force evaluation, over the box volume), vol (A^3), density
-        (g/cm^3), ecouple (the chain's energy, 0 without set_nvt) and econserve = etotal + ecouple.  The pressure entries are NaN
+        (g/cm^3), ecouple (the chain's energy, 0 without set_nvt; with set_npt the barostat's part as well, and vol and density follow the
+        box of the record) and econserve = etotal + ecouple.  The pressure entries are NaN
         without ``vflag``, and while constraints are set (the constraint virial is not accumulated).  One rank on the device.  The
         first call also sums the masses for the density, once."""
         if self.dc.multi or not self._fused:
@@ -939,13 +1124,17 @@ class VerletRun:
                                     work=torch.empty(self._md.ani_md_thermo_work_size(n), dtype=torch.float64, device=self.device),
                                     out=torch.zeros(ani_hip.THERMO_N, dtype=torch.float64, device=self.device))
         b = self._thermo_buf
-        vol = float(np.prod(self._box_len_np))
+        npt_rec = self._npt_read_box() if self._npt is not None else None
+        vol = float(np.prod(self._box_len_np)) if npt_rec is None else float(npt_rec[49])
         self._check(self._md.ani_md_thermo(self.v.data_ptr(), b["mass"].data_ptr(), n, self.ev.data_ptr(),
                                            1 if (self.vflag and self._cons is None) else 0, 3.0 * n - 3.0 - self._ncons, vol,
                                            self._nvt["state"].data_ptr() if self._nvt is not None else None, b["work"].data_ptr(),
                                            b["out"].data_ptr(), self._stream))
         rec = dict(zip(ani_hip.THERMO_KEYS, b["out"].cpu().tolist()))
         del rec["k2"]
+        if npt_rec is not None:       # the barostat's part: chain, strain rate and p_target (V - V0)
+            rec["ecouple"] += float(npt_rec[21])
+            rec["econserve"] = rec["etotal"] + rec["ecouple"]
         rec["density"] = b["mtot"] / vol / 0.602214129      # g/mol/A^3 -> g/cm^3 (LAMMPS units real, mv2d)
         return rec
 
