@@ -198,12 +198,9 @@ void launch_prepare(const int* d_species, const int* d_ilist, const int* d_numne
 void launch_list_symmetry(const int* d_ilist, const int* d_nbr_off, const int* d_numneigh, const int* d_jraw, const int* d_row_of_atom,
                           int nlocal, int ntotal, unsigned* d_acc, int* d_out, hipStream_t st);
 
-#ifndef ANI_TK_GROUPS
-#define ANI_TK_GROUPS 64
-#endif
-constexpr int kTicketGroups = ANI_TK_GROUPS;   // row-ticket counters of a fused forward launch (AevArgs::row_counter) ...
+constexpr int kTicketGroups = 64;               // row-ticket counters of a fused forward launch (AevArgs::row_counter) ...
 constexpr int kTicketMaxGroups = 256;            // what the counter block of a row range has room for
-static_assert(kTicketGroups <= kTicketMaxGroups, "ANI_TK_GROUPS");
+static_assert(kTicketGroups <= kTicketMaxGroups, "kTicketGroups");
 constexpr int kTicketStride = 64;   // ... one per 256 bytes: {next ticket, waves done, -...}
 struct AevArgs {
   const float4* xyzs;

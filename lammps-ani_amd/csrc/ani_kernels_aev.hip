@@ -37,15 +37,12 @@ namespace ani {
 
 constexpr int kWaves = 4;    // centres per workgroup: forward fast path and generic kernels
 constexpr int kWavesB = 4;   // backward fast path
-#ifndef ANI_BWD_MINW
-#define ANI_BWD_MINW 4
-#endif
-#ifndef ANI_FWD_MINW
-#define ANI_FWD_MINW 4
-#endif
-#ifndef ANI_FUSED_MINW
-#define ANI_FUSED_MINW 4
-#endif
+// waves per SIMD the fast kernels are compiled for (the second __launch_bounds__ argument).  Forcing more was measured and
+// not taken (profiles/r03_ablation_notes.md): backward 5 -> 0.294 against 0.297 ms (noise), 6 -> spills; forward 7 -> 0.209
+// against 0.207 ms.
+constexpr int kBwdMinWaves = 4;
+constexpr int kFwdMinWaves = 4;
+constexpr int kFusedMinWaves = 4;
 constexpr int kAevMax = 1024;   // LDS floats reserved for one AEV row (ANI-2x: 1008)
 constexpr int kMaxBuckets = 36; // species pairs on the fast path (S <= 8)
 
@@ -67,21 +64,12 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
   return v;
 }
-#ifdef ABL_FAKE_TRANS   // timing experiment only (wrong results): every transcendental replaced by one multiply-add
-__device__ __forceinline__ float fexp2(float x) { return fmaf(x, 0.001f, 1.0f); }
-__device__ __forceinline__ float flog2(float x) { return fmaf(x, 0.5f, -0.5f); }
-__device__ __forceinline__ float frcp(float x) { return fmaf(x, -0.1f, 1.0f); }
-__device__ __forceinline__ float frsq(float x) { return fmaf(x, -0.1f, 1.0f); }
-__device__ __forceinline__ float fcos_rev(float rev) { return fmaf(rev, -0.5f, 1.0f); }
-__device__ __forceinline__ float fsin_rev(float rev) { return fmaf(rev, 0.5f, 0.1f); }
-#else
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float flog2(float x) { return __builtin_amdgcn_logf(x); }
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float frsq(float x) { return __builtin_amdgcn_rsqf(x); }
 __device__ __forceinline__ float fcos_rev(float rev) { return __builtin_amdgcn_cosf(rev); }  // cos(2 pi rev)
 __device__ __forceinline__ float fsin_rev(float rev) { return __builtin_amdgcn_sinf(rev); }
-#endif
 constexpr float kLog2e = 1.4426950408889634f;
 
 // diagnostic build (-DABLB_STAMPS): wave 0 of every backward workgroup adds the shader-clock cycles it spent in each phase
@@ -173,12 +161,7 @@ void launch_sort_jlist(const int* d_species, const int* d_nbr_off, const int* d_
 // the CU's LDS blocked meanwhile -- whereas ds_add_f64 takes 8 cycles per wave-instruction, like the integer adds
 // (tools/lds_rmw_probe.hip, profiles/r03_lds_rmw_probe.log).  So the accumulators are doubles: one v_cvt_f64_f32 per
 // value added, 6 instead of 3 words per neighbour, and sums that are more accurate on top.
-#ifdef ANI_GD_F32
-typedef float gd_t;
-#else
-typedef double gd_t;
-#endif
-constexpr int kGdWords = 3 * (int)(sizeof(gd_t) / 4);   // LDS words per angular neighbour
+constexpr int kGdWords = 6;   // LDS words per angular neighbour: three doubles
 
 struct FastLds {
   // carved from dynamic LDS, per wave
@@ -193,34 +176,17 @@ struct FastLds {
   float* rr;      // [cap] forward: radial list r
   float* rfc;     // [cap] forward: fc(r; Rcr)
   int* aj;        // [kMaxAng] backward: atom index of the angular neighbours
-  gd_t* gd;       // [3*kMaxAng] backward: dE/d(displacement) of the angular neighbours (fp64: see gd_t)
+  double* gd;     // [3*kMaxAng] backward: dE/d(displacement) of the angular neighbours (fp64: see above)
   float* gt;      // [3*64] backward: staging of one chunk of radial-only gradients for the force scatter
   int* jt;        // [64]   ... and of their atom indices
-  int4* rowd;     // [2*32] backward: descriptors of 32 rows of the pair stream (build_row_descriptors)
-  float4* rowacc; // [2*64] backward, experiment ANI_PARK_ROWS only: per-row sums of the gradients w.r.t. the rows' neighbours
 };
 
-#ifdef ANI_PARK_ROWS
-constexpr int kParkWords = 256;
-#else
-constexpr int kParkWords = 0;
-#endif
-// lanes per row of the backward pair stream (a DPP quad): narrow rows waste few lanes on buckets of 5..12 columns
-#ifndef ANI_ROW_W
-#define ANI_ROW_W 16
-#endif
-constexpr int kRowW = ANI_ROW_W;
-#ifdef ANI_BWD_ROWS
-constexpr int kRowdWords = 256;   // descriptors of 32 rows of the row-layout pair stream
-#else
-constexpr int kRowdWords = 0;
-#endif
 __host__ __device__ constexpr int fast_wave_floats(int cap, bool bwd) {
   // both: ad 4*kMaxAng + row kAevMax + tb kMaxBuckets*8 + starts 2*24
   // forward adds afc, the phase-1 factor buffers pf (64*12) and r, fc per radial neighbour;
   // backward adds afc, aj and gd[3] (fp64) per ANGULAR neighbour and the 4*64 staging words (the radial-only neighbours never
   // touch LDS)
-  return 4 * kMaxAng + kAevMax + kMaxBuckets * 8 + 48 + (bwd ? (2 + kGdWords) * kMaxAng + 256 + kRowdWords + kParkWords : kMaxAng + 64 * 12 + 2 * cap);
+  return 4 * kMaxAng + kAevMax + kMaxBuckets * 8 + 48 + (bwd ? (2 + kGdWords) * kMaxAng + 256 : kMaxAng + 64 * 12 + 2 * cap);
 }
 // same with the AEV row sized for the columns actually in use (rowf floats, multiple of 64)
 // ... and the bucket table for the species pairs of the model in use (S (S + 1) / 2 entries of 8 words: 3 for pruned water, 28 for
@@ -248,16 +214,10 @@ __device__ __forceinline__ FastLds carve(float* base, int cap, bool bwd, int row
     L.tb = reinterpret_cast<int*>(p);   // sized by the model's species count (table_words): last
   } else {
     L.aj = reinterpret_cast<int*>(p); p += kMaxAng;
-    L.gd = reinterpret_cast<gd_t*>(p); p += kGdWords * kMaxAng;   // 8-byte aligned: every piece in front of it is an even number of words
+    L.gd = reinterpret_cast<double*>(p); p += kGdWords * kMaxAng;   // 8-byte aligned: every piece in front of it is an even number of words
     L.afc = p; p += kMaxAng;
     L.gt = p; p += 3 * 64;
     L.jt = reinterpret_cast<int*>(p); p += 64;
-#ifdef ANI_BWD_ROWS
-    L.rowd = reinterpret_cast<int4*>(p); p += 256;
-#endif
-#ifdef ANI_PARK_ROWS
-    L.rowacc = reinterpret_cast<float4*>(p); p += 256;
-#endif
     L.row = p; p += rowf;
     L.tb = reinterpret_cast<int*>(p);
   }
@@ -675,11 +635,8 @@ __device__ __forceinline__ void stream_pair_half(const FastLds& L, int nbk, int 
   ib = e0.w + b;
 }
 
-#ifdef ABL_NO_TWRITE
-#define TILE_ADD(p, v) asm volatile("" ::"v"(p), "v"(v))
-#else
-#define TILE_ADD(p, v) atomicAdd(p, (gd_t)(v))
-#endif
+// one add to a neighbour's fp64 gradient accumulator in LDS (FastLds::gd)
+__device__ __forceinline__ void gd_add(double* p, float v) { atomicAdd(p, (double)v); }
 // v + v[lane ^ OFF] without an LDS round trip: OFF = 1, 2, 4, 8 as DPP moves inside a row of 16 lanes, OFF = 16 / 32
 // with the gfx950 row / half-wave swaps (both operands the same register: one result holds the even rows or the lower
 // half everywhere, the other the odd rows or the upper half)
@@ -704,90 +661,6 @@ __device__ __forceinline__ float xor_sum(float v) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
   }
 }
-// Backward enumeration.  Every non-empty species-pair bucket is laid out as ROWS of kRowW lanes (4: one DPP quad):
-//   s1 != s2 : row = neighbour of one species, column = neighbour of the other, oriented so that the bucket needs the
-//              fewer rows of the stream;
-//   s1 == s2 : the strict upper triangle of n x n folded into nn/2 rows x nn columns (nn = n rounded up to even):
-//              lane (r, c) holds the pair (r, c) if c > r and the pair (nn-1-r, nn-1-c) if c < r;
-//   more than kRowW columns: the row is cut into column blocks of kRowW, each its own row of the stream.
-// The rows of all buckets form one stream; a step of the pair loop takes 64 / kRowW consecutive rows (64 lanes),
-// whatever buckets they belong to.  A pair's gradient with respect to its ROW neighbour is summed over the row with
-// DPP adds (no LDS), lane 0 of the row adds the sum to that neighbour's LDS accumulator; the gradient with respect to
-// the COLUMN neighbour goes to its accumulator with one LDS float add per lane.  Rows were 16 lanes wide at first: with
-// the 5..12 neighbours per species of a typical centre that left 40 % of the lanes of a step idle (water: 153 pairs in
-// 4 steps of 64); quads waste at most three lanes per row (the same 153 pairs in 3 steps), and the arithmetic of the
-// pairs, not the bookkeeping around it, is what this pass spends its time on.  (The very first version issued six LDS
-// float atomics per pair with ~10-way address conflicts, which cost more than all of its arithmetic.)
-// entry: {row0, ra, nr, ca, nc, outoff, tri, column blocks}.  Returns the number of rows in the stream.
-template <int NA, int NZ>
-__device__ __forceinline__ int build_row_table(const AevParams& p, int lane, FastLds& L, int& nbk) {
-  const int nb_all = p.S * (p.S + 1) / 2;
-  int s1 = 0, s2 = 0, ra = 0, nr = 0, ca = 0, nc = 0, nrow = 0, ncb = 1, tri = 0;
-  if (lane < nb_all) {
-    int rem = lane;
-    while (rem >= p.S - s1) { rem -= p.S - s1; s1++; }
-    s2 = s1 + rem;
-    const int a1 = L.astart[s1], a2 = L.astart[s2];
-    const int n1 = L.astart[s1 + 1] - a1, n2 = L.astart[s2 + 1] - a2;
-    int nrows = 0, ncols = 0;
-    if (s1 == s2) {
-      tri = 1;
-      ra = ca = a1; nr = nc = n1;
-      const int nn = (n1 + 1) & ~1;
-      if (n1 >= 2) { nrows = nn >> 1; ncols = nn; }
-    } else if (n1 > 0 && n2 > 0) {
-      // the orientation that takes fewer rows of kRowW lanes
-      const bool sw = n2 * ((n1 + kRowW - 1) / kRowW) < n1 * ((n2 + kRowW - 1) / kRowW);
-      ra = sw ? a2 : a1; nr = sw ? n2 : n1;
-      ca = sw ? a1 : a2; nc = sw ? n1 : n2;
-      nrows = nr; ncols = nc;
-    }
-    if (nrows > 0) {
-      ncb = (ncols + kRowW - 1) / kRowW;
-      nrow = nrows * ncb;
-    }
-  }
-  const int incl = wave_incl_scan(nrow);
-  const unsigned long long m = __ballot(nrow > 0);
-  if (nrow > 0) {
-    int* e = L.tb + 8 * lanes_below(m);
-    e[0] = incl - nrow; e[1] = ra; e[2] = nr; e[3] = ca; e[4] = nc;
-    e[5] = p.radial_len + lane * (NA * NZ); e[6] = tri; e[7] = ncb;
-  }
-  nbk = __popcll(m);
-  return __builtin_amdgcn_readlane(incl, 63);
-}
-
-// Descriptors of rows RB .. RB+31 of the backward pair stream, one lane per row, so that the per-pair lanes of a step
-// (4 rows x 16 lanes) read what they need about their row with two 16-byte LDS loads instead of each repeating the
-// bucket search, the division by the column-block count and the fold arithmetic (that prologue was ~90 of the ~480
-// vector instructions of a step):
-//   d0 = {row neighbour of the pairs above the diagonal (all pairs of a rectangular bucket), row neighbour of the folded
-//         pairs below it (-1: none), first column neighbour of the bucket, number of columns}
-//   d1 = {first column of this row's block, r | tri << 16 | valid << 17, nn (columns of the folded triangle), offset of
-//         the bucket's dE/dAEV block}
-constexpr int kRowBlock = 32;   // rows of the pair stream whose descriptors are held at a time
-__device__ __forceinline__ void build_row_descriptors(FastLds& L, int nbk, int nrows_stream, int RB, int lane) {
-  const int R = RB + lane;
-  int4 d0 = make_int4(0, -1, 0, 0), d1 = make_int4(0, 0, 0, 0);
-  if (R < nrows_stream) {
-    int e = 0;
-    for (int k = 1; k < nbk; k++)
-      if (R >= L.tb[8 * k]) e = k;
-    const int4 e0 = *reinterpret_cast<const int4*>(L.tb + 8 * e);       // row0, ra, nr, ca
-    const int4 e1 = *reinterpret_cast<const int4*>(L.tb + 8 * e + 4);   // nc, outoff, tri, ncb
-    const int u = R - e0.x;
-    const int r = e1.w > 1 ? u / e1.w : u;
-    const int nn = (e0.z + 1) & ~1;
-    const int rb = nn - 1 - r;
-    d0 = make_int4(e0.y + r, (e1.z && rb < e0.z) ? e0.y + rb : -1, e0.w, e1.x);
-    d1 = make_int4((u - r * e1.w) * kRowW, r | (e1.z ? 1 << 16 : 0) | (1 << 17), nn, e1.y);
-  }
-  if (lane < kRowBlock) {
-    L.rowd[2 * lane] = d0;
-    L.rowd[2 * lane + 1] = d1;
-  }
-}
 
 // forward_compute: the AEV row of one centre from the wave's LDS lists (radial list grouped by species, angular list, group
 // starts) -- filled from the compact list by forward_centre, or straight from the candidate list by the fused kernel
@@ -810,7 +683,6 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
   constexpr int NR = 16, Q = 64 / NA;
 
   // ---- radial: per species group, lanes = (slot q, shift k) ----
-#ifndef ABLF_NO_RAD
   {
     const int q = lane >> 4, k = lane & 15;
     const float shf = fmaf((float)k, p.dShfR, p.ShfR0);
@@ -834,7 +706,6 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
       if (q == 0) L.row[s * NR + k] = 0.25f * acc;
     }
   }
-#endif
 
   BWD_STAMP(3);   // radial
   // ---- angular ----
@@ -884,11 +755,7 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
     for (int z = 0; z < NZ; z++) acc[z] = 0.f;
   };
 
-#ifdef ABLF_NO_ANG
-  for (int base = 0; base < 0; base += 64) {
-#else
   for (int base = 0; base < total; base += 64) {
-#endif
     // phase 1: lane = pair
     int outoff;
     {
@@ -1028,7 +895,7 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
   ANI_TICKETS_END(KW)
 
 template <int NA, int NZ, int NCH>
-__global__ __launch_bounds__(64 * kWaves, ANI_FWD_MINW) void aev_forward_fast(AevParams p, AevArgs a, int cap, int rowf) {
+__global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(AevParams p, AevArgs a, int cap, int rowf) {
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   FastLds L = carve<NA, NZ>(reinterpret_cast<float*>(smem4) + wave * fast_wave_floats_row(cap, false, rowf, p.S), cap, false, rowf);
@@ -1066,7 +933,7 @@ __global__ __launch_bounds__(64 * kWaves, ANI_FWD_MINW) void aev_forward_fast(Ae
 // written -- the backward kernel starts from them.  Candidate lists longer than 64 NCHC entries, or AEV shapes off the fast
 // path, take the two kernels.
 template <int NA, int NZ, int NCHC>
-__global__ __launch_bounds__(64 * kWaves, ANI_FUSED_MINW) void aev_forward_fused(AevParams p, AevArgs a, int cap, int rowf) {
+__global__ __launch_bounds__(64 * kWaves, kFusedMinWaves) void aev_forward_fused(AevParams p, AevArgs a, int cap, int rowf) {
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   FastLds L = carve<NA, NZ>(reinterpret_cast<float*>(smem4) + wave * fast_wave_floats_row(cap, false, rowf, p.S), cap, false, rowf);
@@ -1194,12 +1061,10 @@ __global__ __launch_bounds__(64 * kWaves, ANI_FUSED_MINW) void aev_forward_fused
 // (spatially ordered) list share requests too.
 template <typename T>
 __device__ __forceinline__ void scatter_neighbours(const AevArgs& a, const T* g, const int* jx, int cnt, int lane) {
-#ifndef ABL_NO_GATOM
   for (int base = 0; base < cnt; base += 16) {
     const int q = base + (lane >> 2), k = lane & 3;
     if (q < cnt && k < 3) atomicAdd(&a.fbuf[4 * jx[q] + k], -(float)g[3 * q + k]);
   }
-#endif
 }
 
 // Per-atom virial (ani_request_atom_virial): the same shape for the nine products of a scattered neighbour -- lane = (list slot,
@@ -1232,9 +1097,7 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
 #pragma unroll
   for (int k = 0; k < NCH; k++) {
     rjp[k] = -1;
-#ifndef ANI_RAD_NOREC
     if (a.row_of_atom && 64 * k + lane < nrad) rjp[k] = a.row_of_atom[cl_index(pf.jj[k])];
-#endif
   }
 #pragma unroll
   for (int c = 0; c < GR; c++)
@@ -1280,7 +1143,6 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     }
     const int t = w;   // angular neighbours: index of the LDS accumulators
     float gx = 0.f, gy = 0.f, gz = 0.f;
-#ifndef ABL_NO_RAD
     const int s = cl_species(j);   // the entry carries its species (cl_pack)
     j = cl_index(j);
     // A pair's two radial terms -- E_centre's and E_neighbour's dependence on their distance -- differ only in the dE/dAEV
@@ -1291,13 +1153,11 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     // scattered as before and comes back through the ghost exchange.  sym: this lane's neighbour is handled that way.
     float gsx = 0.f, gsy = 0.f, gsz = 0.f;   // sym: what the centre adds to its own force beyond (gx, gy, gz)
     int rj = -1;
-#ifndef ANI_RAD_NOREC
     if (c < NCH) {
 #pragma unroll
       for (int k = 0; k < NCH; k++)
         if (c == k) rj = rjp[k];
     } else if (a.row_of_atom && live) rj = a.row_of_atom[j];
-#endif
     const bool sym = rj >= 0;
     if (live) {
       const float4* gg4 = reinterpret_cast<const float4*>(L.row + s * NR);
@@ -1306,7 +1166,6 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
       const float fc = 0.5f * fcos_rev(r * rev) + 0.5f;
       const float dfc = -0.5f * p.pi_over_Rcr * fsin_rev(r * rev);
       float dEdr = 0.f, dEdn = 0.f;   // d/dr of the centre's energy, of the neighbour's
-#ifndef ANI_RAD_NOREC
       // The sixteen Gaussians exp2(cR (r - ShfR_k)^2) from six exponentials: in each half of the shifts, around its midpoint
       // sc, d_k = dc - m Delta (m = k - 3.5) and exp2(cR d_k^2) = E H^(2m) C_|m| with E = exp2(cR dc^2), H = exp2(-cR dc Delta),
       // C_m = exp2(cR m^2 Delta^2) (wave-uniform).  A transcendental takes the issue time of ~5 FMAs (tools/issue_probe.hip).
@@ -1340,20 +1199,6 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
           }
         }
       }
-#else
-      float dr = r - p.ShfR0;   // equidistant shifts
-#pragma unroll
-      for (int k4 = 0; k4 < NR / 4; k4++) {
-        const float4 gv = gg4[k4];
-        const float gk[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-          const float e = fexp2(cR * dr * dr);
-          dEdr = fmaf(gk[kk] * e, fmaf(-2.f * p.EtaR * dr, fc, dfc), dEdr);
-          dr -= p.dShfR;
-        }
-      }
-#endif
       const float inv_r = frcp(r);
       const float sc = 0.25f * dEdr * inv_r, scn = 0.25f * dEdn * inv_r;
       gx = sc * v.x; gy = sc * v.y; gz = sc * v.z;
@@ -1391,7 +1236,6 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
       ov[3] += v.y * gsx; ov[4] += v.y * gsy; ov[5] += v.y * gsz;
       ov[6] += v.z * gsx; ov[7] += v.z * gsy; ov[8] += v.z * gsz;
     }
-#endif
     if (live && ang) {
       L.ad[t] = v;
       L.afc[t] = 0.5f * fcos_rev(v.w * revA) + 0.5f;
@@ -1435,25 +1279,21 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     }
   }
   BWD_STAMP(2);   // radial stage incl. the radial-only scatter
-#ifndef ANI_BWD_ROWS
   // ---- angular, dense pair stream (round 3).  The pairs of all non-empty species-pair buckets form ONE stream, bucket after
   // bucket, that a step takes 64 lanes of whatever buckets they belong to: a water centre's 153 pairs are 3 steps (the row
-  // layout kept below under ANI_BWD_ROWS, one 16-lane row per row neighbour, needed 4: 60 % of its lanes held a pair).  The
-  // two half-waves walk the stream's column slots together, on two adjacent row neighbours (build_pair_table).  The pairs of
-  // a half-wave that share their ROW neighbour are consecutive lanes (a run): its gradient is summed over the run by a
-  // segmented scan inside each 16-lane DPP row -- level d adds the value d lanes down if that lane belongs to the same run --
-  // and the last lane of the run in its DPP row adds the partial sum to the neighbour's LDS accumulator.  The COLUMN
-  // neighbour's gradient: the two half-waves' values summed with a half-wave swap, one LDS add per lane of the lower half.
+  // layout it replaced, one 16-lane row per row neighbour, needed 4: 60 % of its lanes held a pair; summing a column's four
+  // rows in registers before one conflict-free add was slower still, 0.434 against 0.407 ms, and so was parking the row sums
+  // in LDS for one add per block of rows: profiles/r02_ablation_notes.md).  The two half-waves walk the stream's column slots
+  // together, on two adjacent row neighbours (build_pair_table).  The pairs of a half-wave that share their ROW neighbour are
+  // consecutive lanes (a run): its gradient is summed over the run by a segmented scan inside each 16-lane DPP row -- level d
+  // adds the value d lanes down if that lane belongs to the same run -- and the last lane of the run in its DPP row adds the
+  // partial sum to the neighbour's LDS accumulator.  The COLUMN neighbour's gradient: one LDS add per lane.
   int nbk;
   const int total_pairs = build_pair_table<NA, NZ>(p, lane, L, nbk);
   wave_sync();
   BWD_STAMP(3);   // pair table
   const float cA = -p.EtaA * kLog2e;
-#ifdef ABL_NO_ANG
-  for (int base = 0; base < 0; base += 64) {
-#else
   for (int base = 0; base < total_pairs; base += 32) {
-#endif
     int ia, ib, outoff, pos;
     bool valid;
     stream_pair_half(L, nbk, base + (lane & 31), lane >> 5, ia, ib, outoff, pos, valid);
@@ -1482,11 +1322,6 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     float drA = rho - p.ShfA0;
 #pragma unroll
     for (int sa = 0; sa < NA; sa++) {
-#ifdef ANI_GG_SPLIT
-      // keep the compiler from loading all NA x NZ dE/dAEV values of the bucket before the first is used (32 registers):
-      // the second half of the shifts is fetched after the first half has been contracted
-      if (sa == NA / 2) asm volatile("" ::: "memory");
-#endif
       const float dr = drA;
       drA -= p.dShfA;   // equidistant shifts
       const float f2 = fexp2(cA * dr * dr);
@@ -1514,21 +1349,10 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     const float tb = (Bq + Cq * fa * dfb) * inv_rb - Aq * cosv * inv_rb * inv_rb;
     const float va[3] = {cc * B.x + ta * A.x, cc * B.y + ta * A.y, cc * B.z + ta * A.z};  // d/d(neighbour ia)
     const float vb[3] = {cc * A.x + tb * B.x, cc * A.y + tb * B.y, cc * A.z + tb * B.z};  // d/d(neighbour ib)
-    // column neighbour: lanes l and l + 32 hold the same one
-    {
-#ifndef ANI_COL_SWAP
-      // one fp64 LDS add per lane and component (the two half-waves' lanes l, l + 32 share the address: a two-way conflict costs
-      // less than the half-wave swap-add that used to halve the number of slow fp32 adds)
-      if (valid) { TILE_ADD(&L.gd[3 * ib], vb[0]); TILE_ADD(&L.gd[3 * ib + 1], vb[1]); TILE_ADD(&L.gd[3 * ib + 2], vb[2]); }
-#else
-      const float c0 = xor_sum<32>(vb[0]), c1 = xor_sum<32>(vb[1]), c2 = xor_sum<32>(vb[2]);
-#ifdef ABL_NO_COLADD2
-      asm volatile("" ::"v"(c0), "v"(c1), "v"(c2));
-#else
-      if (valid && lane < 32) { TILE_ADD(&L.gd[3 * ib], c0); TILE_ADD(&L.gd[3 * ib + 1], c1); TILE_ADD(&L.gd[3 * ib + 2], c2); }
-#endif
-#endif
-    }
+    // column neighbour: lanes l and l + 32 hold the same one.  One fp64 LDS add per lane and component (the two half-waves'
+    // lanes l, l + 32 share the address: a two-way conflict costs less than the half-wave swap-add that used to halve the
+    // number of slow fp32 adds)
+    if (valid) { gd_add(&L.gd[3 * ib], vb[0]); gd_add(&L.gd[3 * ib + 1], vb[1]); gd_add(&L.gd[3 * ib + 2], vb[2]); }
     // row neighbour: segmented inclusive scan over the run, inside the lane's 16-lane DPP row
     float rs[3] = {va[0], va[1], va[2]};
 #pragma unroll
@@ -1543,186 +1367,9 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
     }
     // the run ends here (for this DPP row) if the next lane starts a run or lies in the next DPP row
     const int pos_next = __builtin_amdgcn_update_dpp(0, pos, 0x101, 0xf, 0xf, true);   // row_shl:1: lane 15 of a row reads 0
-    if (valid && pos_next == 0) { TILE_ADD(&L.gd[3 * ia], rs[0]); TILE_ADD(&L.gd[3 * ia + 1], rs[1]); TILE_ADD(&L.gd[3 * ia + 2], rs[2]); }
+    if (valid && pos_next == 0) { gd_add(&L.gd[3 * ia], rs[0]); gd_add(&L.gd[3 * ia + 1], rs[1]); gd_add(&L.gd[3 * ia + 2], rs[2]); }
   }
   wave_sync();   // gd is complete
-#else
-  int nbk;
-  const int nrows_stream = build_row_table<NA, NZ>(p, lane, L, nbk);
-  wave_sync();
-  BWD_STAMP(3);   // row table
-
-  // ---- angular: lane = pair; 4 rows of the stream per step (see build_row_table) ----
-  const float cA = -p.EtaA * kLog2e;
-#ifdef ABL_NO_ANG
-  for (int RB = 0; RB < 0; RB += kRowBlock) {
-#else
-  for (int RB = 0; RB < nrows_stream; RB += kRowBlock) {
-#endif
-   build_row_descriptors(L, nbk, nrows_stream, RB, lane);
-   wave_sync();
-   for (int R0 = RB; R0 < min(RB + kRowBlock, nrows_stream); R0 += 64 / kRowW) {
-    const int rl = R0 - RB + lane / kRowW;
-    const int4 d0 = L.rowd[2 * rl], d1 = L.rowd[2 * rl + 1];
-    const bool row_ok = (d1.y >> 17) & 1, tri = (d1.y >> 16) & 1;
-    const int r = d1.y & 0xffff, nn = d1.z;
-    const int col = d1.x + lane % kRowW;
-    const bool above = !tri || col > r;   // tri: which of the two folded pairs this lane holds
-    const int b = above ? col : nn - 1 - col;
-    const bool valid = row_ok && b < d0.w && (!tri || col != r) && (above || d0.y >= 0);
-    // masked lanes: two distinct neighbours keep the geometry finite
-    const int ia = (valid && !above) ? d0.y : d0.x;
-    const int ib = d0.z + (valid ? b : ((tri && r == 0) ? 1 : 0));
-    const float4 A = L.ad[ia], B = L.ad[ib];
-    const float inv_ra = frcp(A.w), inv_rb = frcp(B.w);
-    const float inv_rr = inv_ra * inv_rb;
-    const float cosv = (A.x * B.x + A.y * B.y + A.z * B.z) * inv_rr;
-    const float c = 0.95f * cosv;
-    const float s2 = fmaxf(1.f - c * c, 1e-12f);
-    const float inv_s = frsq(s2);
-    const float sn = s2 * inv_s;
-    const float fa = L.afc[ia], fb = L.afc[ib];
-    const float dfa = -0.5f * p.pi_over_Rca * fsin_rev(A.w * revA);
-    const float dfb = -0.5f * p.pi_over_Rca * fsin_rev(B.w * revA);
-    const float rho = 0.5f * (A.w + B.w);
-    float f1[NZ], df1[NZ];
-#pragma unroll
-    for (int z = 0; z < NZ; z++) {
-      const float bz = fmaxf(0.5f * (1.f + c * p.cosZ[z] + sn * p.sinZ[z]), 0.f);
-      const float pm1 = fexp2((p.Zeta - 1.f) * flog2(bz));
-      f1[z] = pm1 * bz;
-      df1[z] = p.Zeta * pm1 * 0.5f * (sn * p.cosZ[z] - c * p.sinZ[z]) * inv_s;
-    }
-    const float4* gg4 = reinterpret_cast<const float4*>(L.row + d1.w);  // outoff is a multiple of NA*NZ
-    float Aq = 0.f, Bq = 0.f, Cq = 0.f;
-    float drA = rho - p.ShfA0;
-#pragma unroll
-    for (int sa = 0; sa < NA; sa++) {
-#ifdef ANI_GG_SPLIT
-      // keep the compiler from loading all NA x NZ dE/dAEV values of the bucket before the first is used (32 registers):
-      // the second half of the shifts is fetched after the first half has been contracted
-      if (sa == NA / 2) asm volatile("" ::: "memory");
-#endif
-      const float dr = drA;
-      drA -= p.dShfA;   // equidistant shifts
-      const float f2 = fexp2(cA * dr * dr);
-      const float df2 = -2.f * p.EtaA * dr * f2;
-      float g1 = 0.f, gd1 = 0.f;
-#pragma unroll
-      for (int z4 = 0; z4 < NZ / 4; z4++) {
-        const float4 gv = gg4[sa * (NZ / 4) + z4];
-        g1 = fmaf(gv.x, f1[4 * z4], g1); gd1 = fmaf(gv.x, df1[4 * z4], gd1);
-        g1 = fmaf(gv.y, f1[4 * z4 + 1], g1); gd1 = fmaf(gv.y, df1[4 * z4 + 1], gd1);
-        g1 = fmaf(gv.z, f1[4 * z4 + 2], g1); gd1 = fmaf(gv.z, df1[4 * z4 + 2], gd1);
-        g1 = fmaf(gv.w, f1[4 * z4 + 3], g1); gd1 = fmaf(gv.w, df1[4 * z4 + 3], gd1);
-      }
-      Aq = fmaf(f2, gd1, Aq);
-      Cq = fmaf(f2, g1, Cq);
-      Bq = fmaf(df2, g1, Bq);
-    }
-    // gradient of this pair w.r.t. the two neighbour displacements; zero for masked lanes
-    const float P = valid ? fa * fb : 0.f;
-    Aq *= 2.f * P * 0.95f;
-    Bq *= P;       // 2 * P * 0.5
-    Cq *= valid ? 2.f : 0.f;
-    const float cc = Aq * inv_rr;
-    const float ta = (Bq + Cq * dfa * fb) * inv_ra - Aq * cosv * inv_ra * inv_ra;
-    const float tb = (Bq + Cq * fa * dfb) * inv_rb - Aq * cosv * inv_rb * inv_rb;
-    const float va[3] = {cc * B.x + ta * A.x, cc * B.y + ta * A.y, cc * B.z + ta * A.z};  // d/d(neighbour ia)
-    const float vb[3] = {cc * A.x + tb * B.x, cc * A.y + tb * B.y, cc * A.z + tb * B.z};  // d/d(neighbour ib)
-#ifndef ABL_NO_LATOM
-    // column neighbour: one LDS add per lane and component
-#ifndef ABL_NO_COLADD
-#if ANI_ROW_W == 16 && defined(ANI_COLREDUCE)   // measured slower (0.434 against 0.407 ms with registers to spare, worse when it spills)
-    // A ds_add_f32 whose lanes hit the same address is serialised per address, and the four rows of a step that belong to
-    // the same bucket and column block share their 16 columns: a 4-way conflict on every column add, ~2/3 of the LDS
-    // time of this pass.  Such a step (wave-uniform test on the rows' keys) sums the four rows in registers first -- two
-    // row / half-wave swaps per value -- and lets ONE row of lanes add, conflict-free.  cA: pairs whose column neighbour
-    // is `col` (all pairs of a rectangular bucket, the above-diagonal ones of a folded triangle); cB: the
-    // below-diagonal ones, whose column neighbour is nn-1-col.
-    const int key = row_ok ? ((d1.w << 8) | (d1.x >> 4)) : -1;   // bucket (its output offset) and column block
-    const int k0 = __builtin_amdgcn_readlane(key, 0), k1 = __builtin_amdgcn_readlane(key, 16),
-              k2 = __builtin_amdgcn_readlane(key, 32), k3 = __builtin_amdgcn_readlane(key, 48);
-    if ((k1 == k0 || k1 < 0) && (k2 == k0 || k2 < 0) && (k3 == k0 || k3 < 0)) {   // wave-uniform
-      const bool tri0 = __builtin_amdgcn_readlane(d1.y, 0) & (1 << 16);
-      float cA[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) cA[k] = xor_sum<32>(xor_sum<16>((valid && above) ? vb[k] : 0.f));
-      if (lane < 16 && col < d0.w) {
-        const int q = d0.z + col;
-        TILE_ADD(&L.gd[3 * q], cA[0]); TILE_ADD(&L.gd[3 * q + 1], cA[1]); TILE_ADD(&L.gd[3 * q + 2], cA[2]);
-      }
-      if (tri0) {
-        float cB[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) cB[k] = xor_sum<32>(xor_sum<16>((valid && !above) ? vb[k] : 0.f));
-        const int colB = nn - 1 - col;
-        if (lane < 16 && colB >= 0 && colB < d0.w) {
-          const int q = d0.z + colB;
-          TILE_ADD(&L.gd[3 * q], cB[0]); TILE_ADD(&L.gd[3 * q + 1], cB[1]); TILE_ADD(&L.gd[3 * q + 2], cB[2]);
-        }
-      }
-    } else
-#endif
-    if (valid) {   // angular list index = index of the LDS accumulators
-      TILE_ADD(&L.gd[3 * ib], vb[0]); TILE_ADD(&L.gd[3 * ib + 1], vb[1]); TILE_ADD(&L.gd[3 * ib + 2], vb[2]);
-    }
-#else
-    asm volatile("" ::"v"(vb[0]), "v"(vb[1]), "v"(vb[2]));
-#endif
-    // row neighbour(s): sums over the 16 lanes of the row, [0..2] for the pairs whose ia is r (all pairs of a
-    // rectangular bucket, the above-diagonal ones of a folded triangle), [3..5] for those whose ia is nn-1-r
-    float rw[6];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { rw[k] = above ? va[k] : 0.f; rw[3 + k] = above ? 0.f : va[k]; }
-#ifndef ABL_NO_ROWDPP
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      rw[k] = xor_sum<2>(xor_sum<1>(rw[k]));
-      if constexpr (kRowW >= 8) rw[k] = xor_sum<4>(rw[k]);
-      if constexpr (kRowW >= 16) rw[k] = xor_sum<8>(rw[k]);
-    }
-#endif
-#ifdef ANI_PARK_ROWS
-    // experiment (slower, kept for the record): row sums parked per row and added once per block of rows
-    if (lane % kRowW == 0) {
-      L.rowacc[2 * rl] = make_float4(rw[0], rw[1], rw[2], 0.f);
-      L.rowacc[2 * rl + 1] = make_float4(rw[3], rw[4], rw[5], 0.f);
-    }
-#elif !defined(ABL_NO_ROWADD)
-    if (lane % kRowW == 0 && row_ok) {
-      {
-        const int q = d0.x;
-        TILE_ADD(&L.gd[3 * q], rw[0]); TILE_ADD(&L.gd[3 * q + 1], rw[1]); TILE_ADD(&L.gd[3 * q + 2], rw[2]);
-      }
-      if (d0.y >= 0) {
-        const int q = d0.y;
-        TILE_ADD(&L.gd[3 * q], rw[3]); TILE_ADD(&L.gd[3 * q + 1], rw[4]); TILE_ADD(&L.gd[3 * q + 2], rw[5]);
-      }
-    }
-#else
-    asm volatile("" ::"v"(rw[0]), "v"(rw[1]), "v"(rw[2]), "v"(rw[3]), "v"(rw[4]), "v"(rw[5]));
-#endif
-#else
-    asm volatile("" ::"v"(va[0]), "v"(va[1]), "v"(va[2]), "v"(vb[0]), "v"(vb[1]), "v"(vb[2]));
-#endif
-   }
-   wave_sync();
-#if defined(ANI_PARK_ROWS) && !defined(ABL_NO_LATOM)
-   if (lane < kRowBlock && RB + lane < nrows_stream) {   // row sums -> accumulators of the rows' neighbours
-     const int4 d0 = L.rowd[2 * lane];
-     const float4 sa = L.rowacc[2 * lane];
-     TILE_ADD(&L.gd[3 * d0.x], sa.x); TILE_ADD(&L.gd[3 * d0.x + 1], sa.y); TILE_ADD(&L.gd[3 * d0.x + 2], sa.z);
-     if (d0.y >= 0) {
-       const float4 sb = L.rowacc[2 * lane + 1];
-       TILE_ADD(&L.gd[3 * d0.y], sb.x); TILE_ADD(&L.gd[3 * d0.y + 1], sb.y); TILE_ADD(&L.gd[3 * d0.y + 2], sb.z);
-     }
-   }
-#endif
-   wave_sync();   // the tables are rewritten by the next block of rows; after the last block: gd is complete
-  }
-
-#endif
   BWD_STAMP(4);   // angular stage
   // ---- the angular neighbours: F_j -= gd_j ; F_i += sum_j gd_j ; virial -= gd (x) d ----
   for (int q = lane; q < nang; q += 64) {
@@ -1767,7 +1414,7 @@ static_assert((fast_wave_floats(0, true) + 3 * 64) * 4 * kWavesB <= 160 * 1024, 
 // AVP: empty, or float* for the armed instantiation (per-atom virial accumulator) -- a parameter pack, so that the unarmed kernels keep
 // their argument list, and with it their instruction stream, exactly as it was
 template <int NA, int NZ, int NCH, int GR, bool VIR, typename... AVP>
-__global__ __launch_bounds__(64 * kWavesB, ANI_BWD_MINW) void aev_backward_fast(AevParams p, AevArgs a, int cap, int rowf, RepTab rep,
+__global__ __launch_bounds__(64 * kWavesB, kBwdMinWaves) void aev_backward_fast(AevParams p, AevArgs a, int cap, int rowf, RepTab rep,
                                                                                 AVP... avp) {
   constexpr bool AV = sizeof...(AVP) > 0;
   float* avir = nullptr;
@@ -2142,16 +1789,15 @@ static int fast_kind(const AevParams& p) {
 // 7.1 A list) 37 % of a uniform neighbourhood -- so 3/4 of the longest list (at least 128 slots) is reserved instead of
 // all of it; the smaller LDS slice is what lets more waves share a CU.  A centre that still overflows raises the
 // capacity error like any other overflow (never a silent truncation), and AevParams::full_cap restores the full size.
-#ifndef ANI_CAP_GRAIN
-#define ANI_CAP_GRAIN 64
-#endif
+// The capacity is rounded up to kCapGrain slots; 32 (a fifth forward workgroup per CU) measured slower: 0.246 against 0.230 ms.
+constexpr int kCapGrain = 64;
 static int radial_cap(const AevParams& p, int max_numneigh) {
   int full = (max_numneigh + 63) / 64 * 64;
   if (full < 64) full = 64;
   if (p.compat || p.full_cap) return full;
   int est = (3 * max_numneigh + 3) / 4;
   if (est < 128) est = 128;
-  est = (est + ANI_CAP_GRAIN - 1) / ANI_CAP_GRAIN * ANI_CAP_GRAIN;   // 32 (a fifth forward workgroup per CU) measured slower: 0.246 against 0.230 ms
+  est = (est + kCapGrain - 1) / kCapGrain * kCapGrain;
   return est < full ? est : full;
 }
 

@@ -160,11 +160,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[N
   }
 }
 
-#ifndef ANI_GEMM_LB2
-#define ANI_GEMM_LB2 3  // workgroups per CU the 64-row variant is compiled for
-#endif
+constexpr int kGemmLb2 = 3;   // workgroups per CU the 64-row variant is compiled for
 template <int WM, int EPI>
-__global__ __launch_bounds__(256, (WM == 4 ? 2 : (WM == 2 ? ANI_GEMM_LB2 : 3))) void gemm_grouped(GroupArgs G) {
+__global__ __launch_bounds__(256, (WM == 4 ? 2 : (WM == 2 ? kGemmLb2 : 3))) void gemm_grouped(GroupArgs G) {
   constexpr int WN = 4 / WM;        // waves along N
   constexpr int R = 32 * WM;        // rows per workgroup
   constexpr int NTW = 8 / WN;       // max 32-column tiles per wave
@@ -237,11 +235,7 @@ __global__ __launch_bounds__(256, (WM == 4 ? 2 : (WM == 2 ? ANI_GEMM_LB2 : 3))) 
   // Every workgroup of a problem streams the SAME Bt slabs; started together they would all hit the same L2 lines
   // (one channel) at the same time.  Each workgroup therefore walks K from its own starting slab and wraps around:
   // the sum over k is the same set of terms in a rotated order.
-#ifdef ANI_GEMM_NO_KROT
-  const int rot = 0;
-#else
   const int rot = (int)((blockIdx.x * 11u) % (unsigned)nkt);
-#endif
   auto slab_k0 = [&](int kt) { int t = kt + rot; if (t >= nkt) t -= nkt; return t << 5; };
   gload(slab_k0(0));
   for (int kt = 0; kt < nkt; kt++) {
@@ -258,9 +252,7 @@ __global__ __launch_bounds__(256, (WM == 4 ? 2 : (WM == 2 ? ANI_GEMM_LB2 : 3))) 
     for (int i = 0; i < 8; i++)
       if (cr + 32 * i < brows) *reinterpret_cast<float4*>(Bs + (cr + 32 * i) * LDS_LD + ck) = pb[i];
     __syncthreads();
-#ifndef ABL_NO_GLOAD
     if (kt + 1 < nkt) gload(slab_k0(kt + 1));
-#endif
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
       const float4 a4 = *reinterpret_cast<const float4*>(As + (32 * wm + lr) * LDS_LD + ks * 8 + 4 * lh);
@@ -268,10 +260,6 @@ __global__ __launch_bounds__(256, (WM == 4 ? 2 : (WM == 2 ? ANI_GEMM_LB2 : 3))) 
       for (int nt = 0; nt < NTW; nt++) {
         if (nt < tcnt) {
           const float4 b4 = *reinterpret_cast<const float4*>(Bs + (32 * (t0 + nt) + lr) * LDS_LD + ks * 8 + 4 * lh);
-#ifdef ABL_NO_MFMA
-          asm volatile("" ::"v"(a4.x), "v"(b4.x), "v"(b4.w), "v"(a4.w));
-          continue;
-#endif
           acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc[nt], 0, 0, 0);
           acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc[nt], 0, 0, 0);
           acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc[nt], 0, 0, 0);
@@ -346,10 +334,8 @@ __global__ __launch_bounds__(256, ((KB == 2 || RT == 2) ? 2 : (WM == 4 ? 2 : 3))
   // affordable with two planes (2 x 25.6 KB per workgroup: three workgroups per CU still fit), not with three.
   // 100 002 atoms: MLP 0.330 -> 0.318 ms.  (Requesting the loads of slab k+2 at the top of the iteration, a second
   // register set: 0.331.)
-#ifndef ANI_X3_STAGES
-#define ANI_X3_STAGES 2
-#endif
-  constexpr int ST = (P == 2 && KB == 1 && RT == 1) ? ANI_X3_STAGES : 1;
+  constexpr int kX3Stages = 2;
+  constexpr int ST = (P == 2 && KB == 1 && RT == 1) ? kX3Stages : 1;
   constexpr int STAGE = (R + 256) * ROW;
   __shared__ uint4 lds4[ST * STAGE / 16];
   unsigned char* As = reinterpret_cast<unsigned char*>(lds4);
@@ -431,11 +417,7 @@ __global__ __launch_bounds__(256, ((KB == 2 || RT == 2) ? 2 : (WM == 4 ? 2 : 3))
   };
 
   const int nkt = (g.kbp + KB - 1) / KB;
-#ifdef ANI_GEMM_NO_KROT
-  const int rot = 0;
-#else
   const int rot = (int)((blockIdx.x * 11u) % (unsigned)nkt);
-#endif
   auto slab = [&](int kt) { int t = kt + rot; if (t >= nkt) t -= nkt; return t * KB; };
   auto stage_write = [&](unsigned char* As, unsigned char* Bs) {
 #pragma unroll
@@ -501,14 +483,12 @@ __global__ __launch_bounds__(256, ((KB == 2 || RT == 2) ? 2 : (WM == 4 ? 2 : 3))
     __syncthreads();
     stage_write(As, Bs);
     __syncthreads();
-#ifndef ABLX_NO_GLOAD
     if (kt + 1 < nkt) gloadB(slab(kt + 1));
 #pragma unroll
     for (int i = 0; i < PA; i++)
 #pragma unroll
       for (int j = 0; j < KB; j++) { pa[i][j] = pan[i][j]; pm[i][j] = pmn[i][j]; }
     if (kt + 2 < nkt) gloadA(slab(kt + 2), pan, pmn);
-#endif
     multiply(As, Bs);
   }
   __syncthreads();

@@ -42,8 +42,6 @@
 
 namespace ani {
 
-// timing-only ablation switches (wrong results): ABLF_NOWAIT no wait for the pieces of a slab, ABLF_NOBAR no barrier in
-// front of a slab, ABLF_NOMMA no MFMAs, ABLF_NODMA no weight loads
 constexpr int kConstBytes = 4096;          // LDS copy of a member's biases / output layer
 constexpr int kFusedLds = kRing * 1024 + kConstBytes;
 static_assert(kFusedLds + 64 <= 160 * 1024, "ring + constants exceed the LDS of a CU");
@@ -118,52 +116,32 @@ __global__ void build_stream_kernel(const float* __restrict__ src, int ld, int r
 
 // ---- the weight slots (bookkeeping: ani_fused_ring.h) ----------------------------------------------------------------
 __device__ __forceinline__ void ring_load_piece(const Ring& r, unsigned char* slot_base, int q0, int k, int lane16) {
-#ifndef ABLF_NODMA
   const unsigned char* g = r.src + (size_t)(q0 + k) * 1024 + lane16;
   unsigned char* l = slot_base + (k << 10);
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-#endif
 }
 // this wave's share (pieces wave, wave + 4, ...) of the next slab of the stream, into the slot after the last one issued.
 // An LDS-DMA instruction holds the wave's issue for 60 cycles and more: a slab's nine to twelve in one burst behind the
 // barrier leave the matrix pipe idle for as long as twenty MFMAs (measured: 0.331 ms per step at 100 002 atoms).  So the
 // loads go one per block (ring_drip, called in front of a block's MFMAs: 0.308 ms; with a burst of the first two or four
 // pieces 0.311 / 0.324), and whatever is left at the next boundary is issued there (ring_flush), before its wait.
-// -DANI_FUSED_NODRIP restores the burst.
-#ifndef ANI_FUSED_NODRIP
-#define ANI_FUSED_DRIP
-#endif
-#ifndef ANI_FUSED_DRIP_HEAD
-#define ANI_FUSED_DRIP_HEAD 0
-#endif
 __device__ __forceinline__ void ring_drip(Ring& r, unsigned char* ring, int lane16) {
-#ifdef ANI_FUSED_DRIP
   if (r.pk < r.pn) {
     ring_load_piece(r, ring + r.pslot * (kSlot << 10), r.pq0, r.pk, lane16);
     r.pk += 4;
   }
-#endif
 }
 __device__ __forceinline__ void ring_flush(Ring& r, unsigned char* ring, int lane16) {
-#ifdef ANI_FUSED_DRIP
   while (r.pk < r.pn) {
     ring_load_piece(r, ring + r.pslot * (kSlot << 10), r.pq0, r.pk, lane16);
     r.pk += 4;
   }
-#endif
 }
 template <int NT1, int NT2, int NT3, int P>
 __device__ __forceinline__ void ring_issue_next(Ring& r, unsigned char* ring, int wave, int lane16) {
   int q0, n, slot;
-  if (ring_take<NT1, NT2, NT3, P>(r, q0, n, slot)) {
-    unsigned char* base = ring + slot * (kSlot << 10);
-#ifdef ANI_FUSED_DRIP
-    int k = wave;
-    for (int i = 0; i < ANI_FUSED_DRIP_HEAD && k < n; i++, k += 4) ring_load_piece(r, base, q0, k, lane16);
-    r.pq0 = q0; r.pslot = slot; r.pn = n; r.pk = k;
-#else
-    for (int k = wave; k < n; k += 4) ring_load_piece(r, base, q0, k, lane16);
-#endif
+  if (ring_take<NT1, NT2, NT3, P>(r, q0, n, slot)) {   // nothing is loaded here: ring_drip / ring_flush issue the pieces
+    r.pq0 = q0; r.pslot = slot; r.pn = n; r.pk = wave;
   }
 }
 // In front of a slab: returns this lane's read address of the slab's first piece.  Every wave waits for its own loads (the
@@ -171,19 +149,12 @@ __device__ __forceinline__ void ring_issue_next(Ring& r, unsigned char* ring, in
 // two back any more, whose slot the next slab's loads -- issued right behind the barrier -- overwrite.  EARLY marks the calls
 // that stand in front of the LAST block of the slab before (the new slab's first fragments are then requested beside that
 // block's MFMAs instead of after them); the scheme is the same for both.
-__device__ __forceinline__ constexpr bool ring_can_go_early(const Ring&, int) { return true; }
 template <int NT1, int NT2, int NT3, int P, bool EARLY>
 __device__ __forceinline__ const unsigned char* ring_boundary(Ring& r, unsigned char* ring, int n, int wave, int lane16, int* err_flag) {
   (void)n; (void)err_flag;
   ring_flush(r, ring, lane16);
-#ifndef ABLF_NOWAIT
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifndef ABLF_NOBAR
   asm volatile("s_barrier" ::: "memory");
-#else
-  asm volatile("" ::: "memory");
-#endif
   const int s = ring_consume(r);
   ring_issue_next<NT1, NT2, NT3, P>(r, ring, wave, lane16);
   return ring + s * (kSlot << 10) + lane16;
@@ -203,21 +174,11 @@ struct FragV { u32x4 p[P]; };
 // block b (P pieces) of the slab at `base`
 template <int P>
 __device__ __forceinline__ void read_frag(const unsigned char* base, int b, FragV<P>& f) {
-#ifdef ABLF_NOLDS   // timing experiment only: no fragment reads (a value the compiler cannot fold)
-#pragma unroll
-  for (int p = 0; p < P; p++) { unsigned x = (unsigned)(size_t)base + b; asm volatile("" : "+v"(x)); f.p[p] = u32x4{x, x, x, x}; }
-  return;
-#endif
 #pragma unroll
   for (int p = 0; p < P; p++) f.p[p] = *reinterpret_cast<const u32x4*>(base + (b * P + p) * 1024);
 }
 template <int P>
 __device__ __forceinline__ void mma_frag(const FragV<P>& a, const FragV<P>& b, f32x16& acc) {
-#ifdef ABLF_NOMMA   // timing experiment only: operands kept alive, no matrix instruction
-#pragma unroll
-  for (int i = 0; i < P; i++) asm volatile("" ::"v"(a.p[i]), "v"(b.p[i]));
-  return;
-#endif
   if constexpr (P == 3) {   // smallest terms first
     const bf16x8 ah = __builtin_bit_cast(bf16x8, a.p[0]), am = __builtin_bit_cast(bf16x8, a.p[1]), al = __builtin_bit_cast(bf16x8, a.p[2]);
     const bf16x8 bh = __builtin_bit_cast(bf16x8, b.p[0]), bm = __builtin_bit_cast(bf16x8, b.p[1]), bl = __builtin_bit_cast(bf16x8, b.p[2]);
@@ -249,11 +210,6 @@ __device__ __forceinline__ void pin(f32x16& t) { asm volatile("" : "+v"(t)); }
 // two fp32 values (elements 2 i, 2 i + 1 of a k-step's fragment) -> word i of every plane
 template <int P>
 __device__ __forceinline__ void split_pair(float x0, float x1, float a_scale, int i, FragV<P>& f) {
-#ifdef ABLF_NOSPLIT   // timing experiment only: no conversion arithmetic (one move per plane)
-#pragma unroll
-  for (int p = 0; p < P; p++) f.p[p][i] = __float_as_uint(x0);
-  return;
-#endif
   if constexpr (P == 3) {
     unsigned h0, m0, l0, h1, m1, l1;
     split3(x0, h0, m0, l0);
@@ -286,28 +242,21 @@ __device__ __forceinline__ void zero_tiles(f32x16 (&X)[NT]) {
 // SIMD: left to itself the compiler (short of registers) reads every fragment right in front of the MFMA that needs it
 // -- an LDS round trip per two MFMAs -- and bunches the conversions and epilogues between the MFMA groups, where the matrix
 // pipe waits for them.
-#ifndef ANI_FUSED_VALU_PER_MFMA
-#define ANI_FUSED_VALU_PER_MFMA 4
-#endif
+// Vector instructions requested behind each MFMA: 3 / 5 / 6 measured 0.338 / 0.330 / 0.332 against 0.330 ms, and no
+// sched_group_barrier at all 0.337: the hints barely matter (profiles/r03_ablation_notes.md).
+constexpr int kValuPerMfma = 4;
 template <int P>
 __device__ __forceinline__ void sched_first_read() {   // the slab's first block has nobody to be requested behind
-#ifndef ABLF_NOSCHED
   __builtin_amdgcn_sched_group_barrier(0x100, P, 0);
-#endif
 }
 template <int P, bool READ>
 __device__ __forceinline__ void sched_block() {
-#ifndef ABLF_NOSCHED
   if constexpr (READ) __builtin_amdgcn_sched_group_barrier(0x100, P, 0);
 #pragma unroll
   for (int i = 0; i < (P == 3 ? 6 : 3); i++) {
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x002, ANI_FUSED_VALU_PER_MFMA, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, kValuPerMfma, 0);
   }
-#ifdef ANI_FUSED_BLOCK_FENCE   // experiment: nothing moves across the end of a block
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-#endif
 }
 
 // acc[NT] += W (stream) * X  with X in registers: KS k-steps, two per slab.  The fragments of block i + 1 are requested before
@@ -407,9 +356,6 @@ struct ConstLayout {
 
 template <int NT>
 __device__ __forceinline__ void epilogue_celu(f32x16 (&X)[NT], const float* b, int h, float inv, float alpha, float inv_alpha) {
-#ifdef ABLF_NOEPI   // timing experiment only
-  return;
-#endif
 #pragma unroll
   for (int nt = 0; nt < NT; nt++)
 #pragma unroll

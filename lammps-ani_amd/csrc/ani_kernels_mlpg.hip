@@ -100,10 +100,10 @@ __device__ __forceinline__ int g_next_slot(int s) { return s + 1 == kGSlots ? 0 
 // 48 of 100 evaluations; 0 of 100 with this form, with or without the s_nop).  Nothing in the code the compiler made for
 // the builtin looked wrong to us; the statement form also keeps the compiler from modelling the LDS write (its own
 // s_waitcnt vmcnt in front of every later ds_read that might alias): the waits are the explicit ones at the slab boundaries.
+// With the builtin, a second drain-and-barrier behind the slab barrier of g_boundary also gave 0 of 60 wrong, an s_sleep 2
+// there 12 of 60 (same log): the cause is still open.
 __device__ __forceinline__ void g_dma(const unsigned char* g, unsigned lds_addr) {
-#ifndef ABLG_NODMA
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(g) : "memory", "m0");
-#endif
 }
 template <int W>
 __device__ __forceinline__ void g_load_piece(RingG& r, unsigned lane16) {
@@ -134,16 +134,8 @@ __device__ __forceinline__ void g_begin(RingG& r, int n, int wave) {
 template <int W>
 __device__ __forceinline__ const unsigned char* g_boundary(RingG& r, int n_next, int wave, unsigned lane16) {
   g_flush<W>(r, lane16);
-#ifndef ABLG_NOWAIT
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
   asm volatile("s_barrier" ::: "memory");
-#ifdef ABLG_DBLBAR   // experiment: a second rendezvous behind a full drain
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-#ifdef ABLG_SLEEP    // experiment: time between the barrier and the first read of the slab
-  asm volatile("s_sleep 2" ::: "memory");
-#endif
   const int s = r.cslot;
   r.cslot = g_next_slot(s);
   g_begin<W>(r, n_next, wave);
@@ -157,11 +149,6 @@ __device__ __forceinline__ void g_read(const unsigned char* base, int b, FragG<P
 }
 template <int P>
 __device__ __forceinline__ void g_mma(const FragG<P>& a, const FragG<P>& b, f32x4g& acc) {
-#ifdef ABLG_NOMMA
-#pragma unroll
-  for (int i = 0; i < P; i++) asm volatile("" ::"v"(a.p[i]), "v"(b.p[i]));
-  return;
-#endif
   if constexpr (P == 3) {   // smallest terms first
     const bf16x8 ah = __builtin_bit_cast(bf16x8, a.p[0]), am = __builtin_bit_cast(bf16x8, a.p[1]), al = __builtin_bit_cast(bf16x8, a.p[2]);
     const bf16x8 bh = __builtin_bit_cast(bf16x8, b.p[0]), bm = __builtin_bit_cast(bf16x8, b.p[1]), bl = __builtin_bit_cast(bf16x8, b.p[2]);
@@ -213,10 +200,7 @@ __device__ __forceinline__ void g_zero(f32x4g (&X)[NT]) {
 // the boundary in front of a slab therefore stands kPF blocks before the slab's first block.  kPF = 2 measured no faster than 1
 // (MLP ms at 12 501 / 25 002 / 100 002 atoms: 0.0576 / 0.0806 / 0.231 against 0.0571 / 0.0789 / 0.227, profiles/r04_mlpg_prefetch_abl.log):
 // the kernel does not wait for fragments, it is bound by what its waves have to issue.
-#ifndef ANI_G_PF
-#define ANI_G_PF 1
-#endif
-constexpr int kPF = ANI_G_PF;
+constexpr int kPF = 1;
 
 // acc[NT] += W (stream) * X, X in registers: KS k-steps, a slab per k-step.  n_after: size of the slab that follows this
 // product's last one in the stream.

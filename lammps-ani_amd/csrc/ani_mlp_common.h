@@ -49,11 +49,6 @@ __device__ __forceinline__ Frag<P> load_frag(const unsigned char* src) {
 }
 template <int P>
 __device__ __forceinline__ void mma_planes(const Frag<P>& a, const Frag<P>& b, f32x16& acc) {
-#ifdef ABLF_NOMMA   // timing experiment only: operands kept alive, no matrix instruction
-  for (int i = 0; i < P; i++)
-    asm volatile("" ::"v"(a.p[i].x), "v"(a.p[i].y), "v"(a.p[i].z), "v"(a.p[i].w), "v"(b.p[i].x), "v"(b.p[i].y), "v"(b.p[i].z), "v"(b.p[i].w));
-  return;
-#endif
   if constexpr (P == 3) {   // smallest terms first
     const bf16x8 ah = __builtin_bit_cast(bf16x8, a.p[0]), am = __builtin_bit_cast(bf16x8, a.p[1]), al = __builtin_bit_cast(bf16x8, a.p[2]);
     const bf16x8 bh = __builtin_bit_cast(bf16x8, b.p[0]), bm = __builtin_bit_cast(bf16x8, b.p[1]), bl = __builtin_bit_cast(bf16x8, b.p[2]);

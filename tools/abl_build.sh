@@ -1,14 +1,22 @@
 #!/bin/bash
-# build ablation variants of libani_hip.so: tools/abl/libani_<NAME>.so with extra -D flags on ani_kernels_aev.hip
-# usage: tools/abl_build.sh NAME "-DABL_X -DABL_Y" [NAME2 "flags2" ...]
+# build variants of libani_hip.so: tools/abl/libani_<NAME>.so with extra flags on ONE kernel file, everything else (flags, object
+# list, the other objects) taken from the Makefile.  The product sources carry only the stamp switches (-DABLB_STAMPS,
+# -DABLB_STAMPS_VM on aev, -DABLF_STAMPS on mlpf); an experiment is a branch, built with this or with plain make.
+# usage: tools/abl_build.sh UNIT NAME "FLAGS" [NAME2 "FLAGS2" ...]      UNIT: aev, mlpf, ... (ani_kernels_<UNIT>.hip)
+#   e.g. tools/abl_build.sh aev STAMPS "-DABLB_STAMPS"    tools/abl_build.sh mlpf STAMPS "-DABLF_STAMPS"
 set -e
-mkdir -p "$(dirname "$0")/abl"
+unit=$1; shift
 cd "$(dirname "$0")/../lammps-ani_amd/csrc"
-OBJS="ani_hip.o ani_model.o ani_kernels_mlp.o ani_kernels_mlpf.o ani_comm.o ani_kernels_misc.o ani_kernels_f64.o ani_kernels_nbr.o ani_kernels_rep.o ani_kernels_md.o"
+[ -f ani_kernels_$unit.hip ] || { echo "no ani_kernels_$unit.hip" >&2; exit 2; }
+make -j8
+mkvar() { make -s --eval="print-var: ; @echo \$($1)" print-var; }
+CXXFLAGS=$(mkvar CXXFLAGS); ROCTX_LIBS=$(mkvar ROCTX_LIBS)
+OBJS=$(mkvar OBJS | tr ' ' '\n' | grep -v "^ani_kernels_$unit.o$")
+mkdir -p ../../tools/abl
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
-  ( hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -I/opt/rocm/include $flags -c ani_kernels_aev.hip -o ../../tools/abl/aev_$name.o &&
-    hipcc -shared -fPIC --offload-arch=gfx950 -o ../../tools/abl/libani_$name.so $OBJS ../../tools/abl/aev_$name.o -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib -ldl && echo built $name ) &
+  ( hipcc $CXXFLAGS $flags -c ani_kernels_$unit.hip -o ../../tools/abl/${unit}_$name.o &&
+    hipcc -shared -fPIC --offload-arch=gfx950 -o ../../tools/abl/libani_$name.so $OBJS ../../tools/abl/${unit}_$name.o $ROCTX_LIBS -ldl && echo built $name ) &
   while [ $(jobs -r | wc -l) -ge 4 ]; do sleep 0.5; done
 done
 wait

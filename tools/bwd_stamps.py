@@ -1,4 +1,4 @@
-"""per-phase cycle counts of the AEV backward kernel (a -DABLB_STAMPS build: tools/abl_build.sh STAMPS "-DABLB_STAMPS"):
+"""per-phase cycle counts of the AEV backward kernel (a -DABLB_STAMPS build: tools/abl_build.sh aev STAMPS "-DABLB_STAMPS"):
 ANI_HIP_LIB=tools/abl/libani_STAMPS.so python tools/bwd_stamps.py [atoms]"""
 import ctypes as C
 import os

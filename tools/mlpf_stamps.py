@@ -1,5 +1,5 @@
 """Where a tile of the fused MLP kernel spends its cycles: run with ANI_HIP_LIB pointing at a -DABLF_STAMPS build
-(tools/abl_build_mlpf.sh STAMPS -DABLF_STAMPS).  usage: python tools/mlpf_stamps.py [atoms] [arith]"""
+(tools/abl_build.sh mlpf STAMPS "-DABLF_STAMPS").  usage: python tools/mlpf_stamps.py [atoms] [arith]"""
 import ctypes as C
 import os
 import sys
