@@ -310,6 +310,68 @@ int ani_md_npt_final_integrate(double* v, const double* f, const double* dtfm, c
                                const double* npt_state, double* work, void* stream);
 int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, double* out, void* stream);
 
+/*
+ * Umbrella restraints on collective variables in the loop: a harmonic bias on a distance, an angle or a torsion (PLUMED `DISTANCE` /
+ * `ANGLE` / `TORSION` + `RESTRAINT`, LAMMPS `fix restrain bond` / `angle`), as two launches behind the force evaluation, and a
+ * device-side series of the values (PLUMED `PRINT`).  fp64 whatever the handle, one rank, no floating-point atomics, nothing
+ * synchronises.
+ *
+ * Tables (device):
+ *   atoms[nr][4]   int32: the 2, 3 or 4 owned atoms of a restraint as local indices (< natoms), all distinct, -1 in unused slots
+ *   kind[nr]       int32: ANI_MD_RESTRAINT_DISTANCE (slots a, b), _ANGLE (a, b, c; b is the apex), _TORSION (a, b, c, d)
+ *   kappa[nr]      >= 0, kcal/mol/A^2 (distance) or kcal/mol/rad^2 (angle, torsion); PLUMED's KAPPA=100 kJ/mol/rad^2 is 23.9006
+ *   centre[nr]     A or rad
+ * Box: len = len3 (host pointer to three doubles) when box_dev == NULL, otherwise the three doubles at box_dev in device memory (the
+ *   loop passes the barostat record's [11..14): the box of the moment).  Every difference vector is a minimum image,
+ *   minimg(a)[k] = a[k] - len[k] rint(a[k] / len[k]) in the periodic dimensions (bit k of periodic_mask).
+ * Bias:  e = kappa / 2 D^2,  F_i = -kappa D dcv/dx_i,  D = cv - centre; for a torsion D is folded into (-pi, pi]:
+ *   D -= 2 pi rint(D / (2 pi)), then D += 2 pi where D <= -pi.
+ * Collective variables:
+ *   distance  r = minimg(x_a - x_b), cv = |r|;  dcv/dx_a = r / |r|, dcv/dx_b = -r / |r|
+ *   angle     u = minimg(x_a - x_b), w = minimg(x_c - x_b), c = u^ . w^ clamped to [-1, 1], cv = acos(c) in [0, pi];  with
+ *             s = sqrt((1 - c) (1 + c)):  dcv/dx_a = (c u^ - w^) / (|u| s),  dcv/dx_c = (c w^ - u^) / (|w| s),  dcv/dx_b = minus their sum
+ *   torsion   F = minimg(x_a - x_b), G = minimg(x_b - x_c), H = minimg(x_d - x_c), A = F x G, B = H x G,
+ *             cv = atan2(-|G| F . B, A . B): the IUPAC / PLUMED sign -- a = (1,0,0), b = (0,0,0), c = (0,0,1), d = (cos t, sin t, 1)
+ *             gives cv = t.  With T = (F . G) / (|A|^2 |G|) A - (H . G) / (|B|^2 |G|) B:
+ *             dcv/dx_a = -|G| / |A|^2 A,  dcv/dx_d = |G| / |B|^2 B,  dcv/dx_b = -dcv/dx_a + T,  dcv/dx_c = -dcv/dx_d - T
+ * Virial of a restraint:  W_ab = sum_i rho_i,a F_i,b  with rho the minimum-image positions relative to slot b: distance r, 0; angle
+ *   u, 0, w; torsion F, 0, -G, H - G.  Nine entries in ev's order, W_ab at 3 a + b.
+ * A restraint whose D or gradient is not finite (a collinear torsion, an angle at 0 or pi, coincident atoms; also a table entry
+ *   that names an atom outside [0, natoms) or an unknown kind, which reads no position) writes e = NaN with zero forces and zero
+ *   virial, and is counted: the NaN reaches ev[0], where the loop's look finds it.
+ *
+ * ani_md_restraints_eval    one thread per restraint, 256-thread blocks, registers only.  Writes cv[nr], e[nr], the slot forces
+ *   fslot[nr][4][3] (zeros in unused slots) and w[nr][9], and nothing else: restraints may share atoms.
+ * ani_md_restraints_apply   reads the host-built gather table in CSR form: touched[ntouched] the atoms in any restraint, ascending;
+ *   row_ptr[ntouched + 1]; entries[row_ptr[t] .. row_ptr[t + 1]) the words 4 restraint + slot of atom touched[t], ascending.  One
+ *   thread per touched atom sums its entries' slot forces in table order into an accumulator that starts from 0, then f[i] += the
+ *   accumulator; rows of atoms in no restraint are not written.  One further workgroup of the same launch sums e and w in the fixed
+ *   order of the chain's sums (per-thread strided accumulators, then the block sum), then  ev[0] += E;  with_virial != 0:
+ *   ev[1..10) += W, otherwise those words are not touched;  and writes the record and, with series_row != NULL, the row
+ *   step, cv[0..nr), e[0..nr)  at series_row (1 + 2 nr doubles: the host chooses the row, there is no device counter).
+ *   The same inputs give bitwise the same f, ev and record.
+ *   A word of the table that points outside -- touched[t] outside [0, natoms), an entry outside [0, 4 nr) -- is skipped (an atom
+ *   with all its entries, or the one entry), never followed, and the sums' workgroup counts such words: any of them makes E NaN
+ *   (ev[0] and record [1]) like a non-finite restraint, so a table that drops force cannot pass for a good one.  row_ptr is
+ *   trusted: ascending, within entries.
+ * Record: ANI_MD_RESTRAINT_NREC doubles on the device, zeroed by the caller at the start:
+ *   [0] evaluations (one more per apply)   [1] E   [2..11) W   [11] non-finite restraints of this evaluation
+ *   [12] the largest |D| among the finite ones   [13] skipped words of the gather table   [14..16) 0
+ * No alignment beyond that of the element types is asked of any pointer.
+ * nr <= 0: both return 0 and launch nothing.
+ */
+#define ANI_MD_RESTRAINT_NREC 16
+#define ANI_MD_RESTRAINT_DISTANCE 0
+#define ANI_MD_RESTRAINT_ANGLE 1
+#define ANI_MD_RESTRAINT_TORSION 2
+int ani_md_restraints_eval(const double* x, int natoms, const int* atoms, const int* kind, const double* kappa, const double* centre,
+                           int nr, const double* len3, const double* box_dev, int periodic_mask, double* cv, double* e, double* fslot,
+                           double* w, void* stream);
+int ani_md_restraints_apply(double* f, int natoms, double* ev, int with_virial, const int* touched, const int* row_ptr,
+                            const int* entries, int ntouched, const double* fslot, const double* cv, const double* e, const double* w,
+                            const double* centre, const int* kind, int nr, double* record, double step, double* series_row,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

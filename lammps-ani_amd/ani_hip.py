@@ -101,6 +101,30 @@ def npt_state_dict(rec, mpchain: int = NH_MAXCHAIN) -> dict:
     return out
 
 
+# the restraint record and the kinds of include/ani_md.h (ani_md_restraints_*): kind -> (code, atoms)
+RESTRAINT_NREC = 16
+RESTRAINT_KINDS = {"distance": (0, 2), "angle": (1, 3), "torsion": (2, 4)}
+
+
+def restraint_gather_table(atoms):
+    """The gather table of ani_md_restraints_apply from atoms [nr, 4] (local indices, -1 unused): (touched [nt] ascending,
+    row_ptr [nt + 1], entries: the words 4 restraint + slot of each touched atom, ascending), all int32."""
+    atoms = np.asarray(atoms, dtype=np.int64).reshape(-1, 4)
+    words = np.flatnonzero(atoms.reshape(-1) >= 0)                 # 4 restraint + slot, ascending
+    owner = atoms.reshape(-1)[words]
+    order = np.argsort(owner, kind="stable")
+    touched, counts = np.unique(owner, return_counts=True)
+    row_ptr = np.concatenate([[0], np.cumsum(counts)])
+    return touched.astype(np.int32), row_ptr.astype(np.int32), words[order].astype(np.int32)
+
+
+def restraint_state_dict(rec) -> dict:
+    """the ANI_MD_RESTRAINT_NREC doubles of a restraint record (host array) as a dict"""
+    rec = np.asarray(rec, dtype=np.float64)
+    return dict(evaluations=int(rec[0]), ebias=float(rec[1]), virial=rec[2:11].reshape(3, 3).copy(), nonfinite=int(rec[11]),
+                max_delta=float(rec[12]), skipped=int(rec[13]))
+
+
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
     """ani_md_fire_params with the defaults of LAMMPS `min_modify` (dtmax = 10 dt0, dtmin = 0.02 dt0, ...); kw overrides them"""
     vals = dict(dt0=float(dt0), dtmax=10.0 * dt0, dtmin=0.02 * dt0, dtgrow=1.1, dtshrink=0.5, alpha0=0.25, alphashrink=0.99,
@@ -237,6 +261,11 @@ def lib():
         L.ani_md_npt_final_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
         L.ani_md_npt_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_restraints_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_restraints_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

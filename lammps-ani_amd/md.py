@@ -169,6 +169,7 @@ class VerletRun:
         self._rdf_every = 0    # radial distribution functions (set_rdf): 0 = none, else a frame every so many steps
         self._nvt = None       # Nose-Hoover chain (set_nvt): None, or the device record, scratch and parameters
         self._npt = None       # isotropic barostat (set_npt): None, or the device record, its check buffers, parameters and targets
+        self._restr = None     # umbrella restraints (set_restraints): None, or the device tables, outputs, record and series
         self._thermo_buf = None
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
@@ -436,7 +437,7 @@ class VerletRun:
         self.since_build += 1
         # Neighbor::decide + check_distance (every N steps, rebuild if any atom moved more than skin/2)
         rebuild = bool(force_rebuild) or (self.since_build % self.every == 0 and self._look() > self._rebuild_limit())
-        self._ghosts_and_forces(rebuild)
+        self._ghosts_and_forces(rebuild, sample=True)
         # on every path above the ghost rows of x are now the images of this step's owned positions
         if self._rdf_every and self.step_no % self._rdf_every == 0:
             self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
@@ -644,16 +645,20 @@ class VerletRun:
             self._reverse_send(self._stream)
             self._reverse_unpack(self._stream)
 
-    def _ghosts_and_forces(self, rebuild: bool):
-        """re-neighbouring or forward ghost positions, then forces and reverse ghost forces, by whichever path the loop is on"""
+    def _ghosts_and_forces(self, rebuild: bool, sample: bool = False):
+        """re-neighbouring or forward ghost positions, then forces and reverse ghost forces, by whichever path the loop is on; then,
+        with restraints set, their two launches on the final owned rows of f (sample: this evaluation may write a series row)"""
         if rebuild:
             self._build_list()
+            self._forces()
         elif self._overlap:
             self._forces_overlapped()
-            return
-        elif not self._fold:   # folded: the pack kernel of the step reads the images' positions from their owners (and writes them to x)
-            self._forward_ghosts(self._stream)
-        self._forces()
+        else:
+            if not self._fold:   # folded: the pack kernel of the step reads the images' positions from their owners (and writes them to x)
+                self._forward_ghosts(self._stream)
+            self._forces()
+        if self._restr is not None:
+            self._restraint_forces(sample)
 
     def minimize(self, etol: float, ftol: float, maxiter: int, dt0=None, check_every=None, on_look=None, **fire_params):
         """``min_style fire`` + ``minimize etol ftol maxiter``: FIRE energy minimisation of the owned atoms without leaving the
@@ -669,6 +674,8 @@ class VerletRun:
         Returns a dict: iterations, stop (etol / ftol / maxiter), energy_before / energy_after, fnorm_before / fnorm_after
         (sqrt(sum f.f) over the owned atoms), force_evaluations, uphill_events, limited_moves, rebuilds.
         On return v is zero, the forces belong to the positions, step_no and the Langevin stream are untouched: ``run`` can follow.
+        With restraints set (set_restraints) the minimised energy includes the bias and every force evaluation is followed by
+        their two launches; no series row is written.
         One rank only: with several, the three sums of an iteration would need an all-reduce each (open lead)."""
         if self.dc.multi:
             raise RuntimeError("VerletRun.minimize: one rank only (the sums of an iteration are not reduced over ranks)")
@@ -981,6 +988,151 @@ class VerletRun:
             raise RuntimeError("VerletRun.constraint_stats: no constraints are set")
         return self._stats_record(self._chk_dev[1:].cpu())
 
+    # ---- umbrella restraints ---------------------------------------------------------------------------------
+    def set_restraints(self, restraints, stride: int = 0, capacity: int = 4096):
+        """PLUMED ``DISTANCE`` / ``ANGLE`` / ``TORSION`` + ``RESTRAINT`` (+ ``PRINT STRIDE=stride``), LAMMPS ``fix restrain bond`` /
+        ``angle``: harmonic restraints on collective variables (ani_md_restraints_eval / ani_md_restraints_apply, include/ani_md.h),
+        fp64 whatever the handle.  restraints: a sequence of (kind, tags, kappa, centre) with kind "distance" (2 global tags),
+        "angle" (3, the middle one the apex) or "torsion" (4); kappa >= 0 in kcal/mol/A^2 or kcal/mol/rad^2 (PLUMED's KAPPA=100
+        kJ/mol/rad^2 is 23.9006), centre in A or rad.  From here on two launches stand behind every force evaluation -- of step(),
+        run() (the one-launch step boundary stays), minimize() and the set-up re-evaluations -- after the ghost forces are folded:
+        the bias force is added to f, the bias energy to ev[0] and, with ``vflag``, the bias virial to ev[1..10), so
+        potential_energy(), thermo() (pe, press, econserve), virial() and the barostat's strain rate see the bias with no change
+        of their own (LAMMPS ``fix_modify energy yes virial yes``).  Under set_npt the restraints take the box from the barostat's
+        device record.  This call builds the tables and evaluates the forces again: f, ev and the record belong to the current
+        positions.  A restraint that is not finite (a collinear torsion, coincident atoms) makes the energy NaN, and the loop's
+        next look raises as for any non-finite energy.
+        stride > 0: every step with step_no % stride == 0 -- and the evaluation of this call, when that holds -- writes the row
+        step, cv, bias energies into a device buffer of `capacity` rows (the host counts and wraps; restraint_series reads).
+        minimize() does not sample.  An empty list clears the restraints: the forces are evaluated again without them and the loop
+        launches what it launched before.  One rank with native re-neighbouring only (the owned atoms keep their order there, so
+        the tables stay valid across rebuilds).  Raises ValueError for an unknown kind, an unknown tag, a repeated tag inside one
+        restraint, a wrong tag count, a negative or non-finite kappa, a non-finite centre, stride < 0 and capacity < 1."""
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.set_restraints: one rank only (a restraint's atoms would have to migrate together)")
+        if not self._native_rebuild:
+            raise RuntimeError("VerletRun.set_restraints needs the device loop with native re-neighbouring (one rank on the GPU)")
+        from . import ani_hip
+        restraints = list(restraints)
+        if int(stride) < 0 or int(capacity) < 1:
+            raise ValueError("VerletRun.set_restraints: stride >= 0 and capacity >= 1")
+        if not restraints:
+            had, self._restr = self._restr is not None, None
+            if had:
+                self._ghosts_and_forces(False)     # f and ev without the bias
+            return
+        local = {int(t): i for i, t in enumerate(self.tag.cpu().numpy().tolist())}
+        nr = len(restraints)
+        atoms = np.full((nr, 4), -1, dtype=np.int32)
+        kind = np.zeros(nr, dtype=np.int32)
+        for r, item in enumerate(restraints):
+            try:
+                name, tags, _, _ = item
+                tags = [int(t) for t in tags]
+            except (TypeError, ValueError):
+                raise ValueError(f"restraint {r}: expected (kind, tags, kappa, centre), got {item!r}") from None
+            if name not in ani_hip.RESTRAINT_KINDS:
+                raise ValueError(f"restraint {r}: unknown kind {name!r} (one of {sorted(ani_hip.RESTRAINT_KINDS)})")
+            kind[r], want = ani_hip.RESTRAINT_KINDS[name]
+            if len(tags) != want:
+                raise ValueError(f"restraint {r}: a {name} takes {want} tags, got {len(tags)}")
+            for t in tags:
+                if t not in local:
+                    raise ValueError(f"restraint {r} ({name}): unknown tag {t}")
+            if len(set(tags)) != len(tags):
+                raise ValueError(f"restraint {r} ({name}): repeated tag in {tuple(tags)}")
+            atoms[r, :want] = [local[t] for t in tags]
+        kappa, centre = self._restraint_windows([it[3] for it in restraints], [it[2] for it in restraints], nr, "set_restraints")
+        touched, row_ptr, entries = ani_hip.restraint_gather_table(atoms)
+        dev = self.device
+
+        def ints(a):
+            return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)
+
+        def zeros(*shape):
+            return torch.zeros(shape, dtype=torch.float64, device=dev)
+
+        self._restr = dict(nr=nr, nt=int(touched.shape[0]), atoms=ints(atoms), kind=ints(kind), kappa=torch.as_tensor(kappa, device=dev),
+                           centre=torch.as_tensor(centre, device=dev), touched=ints(touched), row_ptr=ints(row_ptr), entries=ints(entries),
+                           cv=zeros(nr), e=zeros(nr), fslot=zeros(nr, 4, 3), w=zeros(nr, 9), rec=zeros(ani_hip.RESTRAINT_NREC),
+                           stride=int(stride), capacity=int(capacity), series=zeros(int(capacity), 1 + 2 * nr) if stride else None,
+                           nsamples=0)
+        self._ghosts_and_forces(False, sample=True)
+
+    @staticmethod
+    def _restraint_windows(centres, kappas, nr: int, where: str):
+        """(kappa [nr], centre [nr]) as float64 arrays, checked; kappas None: not given"""
+        try:
+            centre = np.array([float(c) for c in centres], dtype=np.float64)
+            kappa = None if kappas is None else np.array([float(k) for k in kappas], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"VerletRun.{where}: kappa and centre must be numbers") from None
+        if centre.shape[0] != nr or (kappa is not None and kappa.shape[0] != nr):
+            raise ValueError(f"VerletRun.{where}: {nr} restraints, {centre.shape[0]} centres"
+                             + ("" if kappa is None else f", {kappa.shape[0]} kappas"))
+        if not np.isfinite(centre).all():
+            raise ValueError(f"VerletRun.{where}: every centre must be finite")
+        if kappa is not None and not (np.isfinite(kappa).all() and (kappa >= 0.0).all()):
+            raise ValueError(f"VerletRun.{where}: every kappa must be finite and >= 0")
+        return kappa, centre
+
+    def set_restraint_centres(self, centres, kappas=None):
+        """move the windows of the restraints that are set (centres [nr]; kappas [nr] or None: as they are) without rebuilding the
+        tables, and evaluate the forces again.  Writes no series row: a step's row holds the window that the step ran in."""
+        rs = self._restr
+        if rs is None:
+            raise RuntimeError("VerletRun.set_restraint_centres: no restraints are set (set_restraints)")
+        kappa, centre = self._restraint_windows(centres, kappas, rs["nr"], "set_restraint_centres")
+        rs["centre"].copy_(torch.as_tensor(centre))
+        if kappa is not None:
+            rs["kappa"].copy_(torch.as_tensor(kappa))
+        self._ghosts_and_forces(False)
+
+    def _restraint_forces(self, sample: bool):
+        """the two launches behind a force evaluation; the box of the moment comes from the barostat's record when there is one"""
+        rs, md, st, n = self._restr, self._md, self._stream, self.nlocal
+        box_dev = self._npt["state"][11:14].data_ptr() if self._npt is not None else None
+        self._check(md.ani_md_restraints_eval(self.x.data_ptr(), n, rs["atoms"].data_ptr(), rs["kind"].data_ptr(), rs["kappa"].data_ptr(),
+                                              rs["centre"].data_ptr(), rs["nr"], self._len3.ctypes.data, box_dev, self._pmask,
+                                              rs["cv"].data_ptr(), rs["e"].data_ptr(), rs["fslot"].data_ptr(), rs["w"].data_ptr(), st))
+        row = None
+        if sample and rs["stride"] and self.step_no % rs["stride"] == 0:
+            row = rs["series"][rs["nsamples"] % rs["capacity"]].data_ptr()
+            rs["nsamples"] += 1
+        self._check(md.ani_md_restraints_apply(self.f.data_ptr(), n, self.ev.data_ptr(), 1 if self.vflag else 0, rs["touched"].data_ptr(),
+                                               rs["row_ptr"].data_ptr(), rs["entries"].data_ptr(), rs["nt"], rs["fslot"].data_ptr(),
+                                               rs["cv"].data_ptr(), rs["e"].data_ptr(), rs["w"].data_ptr(), rs["centre"].data_ptr(),
+                                               rs["kind"].data_ptr(), rs["nr"], rs["rec"].data_ptr(), float(self.step_no), row, st))
+
+    def restraint_state(self) -> dict:
+        """the restraints' device record and outputs of the last evaluation (one synchronising read each): evaluations, ebias (the
+        bias energy that is in ev[0]), virial [3, 3], nonfinite, max_delta (largest |cv - centre|, torsions folded), skipped (words of the gather
+        table that point outside: always 0 with the table this class builds), and cv [nr], energy [nr]"""
+        rs = self._restr
+        if rs is None:
+            raise RuntimeError("VerletRun.restraint_state: no restraints are set (set_restraints)")
+        from .ani_hip import restraint_state_dict
+        out = restraint_state_dict(rs["rec"].cpu().numpy())
+        out.update(cv=rs["cv"].cpu().numpy(), energy=rs["e"].cpu().numpy())
+        return out
+
+    def restraint_series(self, reset: bool = False) -> dict:
+        """The rows written so far, in time order: step [ns], cv [ns, nr], ebias [ns, nr], and dropped (rows overwritten because
+        more than `capacity` were written since the last reset).  One copy of the buffer; synchronises only here.  reset: start
+        an empty series afterwards."""
+        rs = self._restr
+        if rs is None:
+            raise RuntimeError("VerletRun.restraint_series: no restraints are set (set_restraints)")
+        nr, cap, ns = rs["nr"], rs["capacity"], rs["nsamples"]
+        if rs["series"] is None or ns == 0:
+            rows = np.zeros((0, 1 + 2 * nr))
+        else:
+            buf = rs["series"].cpu().numpy()
+            rows = buf[:ns] if ns <= cap else np.concatenate([buf[ns % cap:], buf[: ns % cap]])
+        if reset:
+            rs["nsamples"] = 0
+        return dict(step=rows[:, 0].astype(np.int64), cv=rows[:, 1:1 + nr].copy(), ebias=rows[:, 1 + nr:].copy(), dropped=max(0, ns - cap))
+
     def _forces_overlapped(self):
         """Forward exchange, PairANI::compute and reverse exchange of a step that keeps its list, the two exchanges on the
         communication stream: the forward one beside the rows without ghosts (pack, compaction, AEV forward), the reverse
@@ -1098,6 +1250,7 @@ class VerletRun:
         return self._allreduce_sum(ke.clone())
 
     def potential_energy(self) -> float:
+        """ev[0] of the last force evaluation summed over ranks: the model's energy plus, with restraints set, their bias"""
         return self._allreduce_sum(self.ev[:1].clone())
 
     def virial(self) -> np.ndarray:
@@ -1112,8 +1265,9 @@ class VerletRun:
         pyz (atm: kinetic tensor plus the pair virial of the last force evaluation, over the box volume), vol (A^3), density
         (g/cm^3), ecouple (the chain's energy, 0 without set_nvt; with set_npt the barostat's part as well, and vol and density follow the
         box of the record) and econserve = etotal + ecouple.  The pressure entries are NaN
-        without ``vflag``, and while constraints are set (the constraint virial is not accumulated).  One rank on the device.  The
-        first call also sums the masses for the density, once."""
+        without ``vflag``, and while constraints are set (the constraint virial is not accumulated).  With restraints set
+        (set_restraints) pe, etotal and econserve include the bias energy and the pressure entries the bias virial.  One rank on
+        the device.  The first call also sums the masses for the density, once."""
         if self.dc.multi or not self._fused:
             raise RuntimeError("VerletRun.thermo: one rank on the device only (the sums are not reduced over ranks)")
         from . import ani_hip
