@@ -1,6 +1,6 @@
 // ani_fused_host.h — what the host needs to drive the fused MLP kernels (mlp_fused16 in ani_kernels_mlpg.hip, mlp_fused in
 // ani_kernels_mlpf.hip): the table of compiled shapes, the sizes that follow from it, and the static schedule of a launch.
-// Plain C++ -- no HIP, no environment -- compiled by the kernel files, by ani_hip.cpp and by stand-alone host programs
+// Plain C++ -- no HIP, no environment -- compiled by the kernel files, by ani_hip_mlp.cpp and by stand-alone host programs
 // (tests/ring_sim.cpp), like ani_fused_ring.h.  Internal to libani_hip.so.
 #pragma once
 

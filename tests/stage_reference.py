@@ -4,7 +4,7 @@ The MLP stage (forward through the ensemble + dE/dAEV) is evaluated here in nump
 (``debug_view().d_aev``), so a difference from the kernel comes from the MLP kernels alone.  Units follow the library:
 ``eatom`` in kcal/mol including the self energy (as ``ANI.compute(...)["eatom"]``), ``gaev`` = the mean over members of
 dE/dAEV in Hartree per AEV unit (as ``d_gaev``: the fused kernels scale the backward seed by ``1/M`` and sum members,
-``ani_hip.cpp``, ``G.scale``; the oracle's ``gaev`` has the same scaling).
+``ani_hip_mlp.cpp``, ``G.scale``; the oracle's ``gaev`` has the same scaling).
 
 Error model of the MLP kernels
 ------------------------------
@@ -20,7 +20,7 @@ u = 2^-24 (fp32 unit roundoff).  Every product of a layer, y_o = sum_k w_ok x_k 
     product of two such operands is good to 2 * 2^-22 + 2^-44 < 9u (rho = 9u).  The low term of a small operand can
     fall below fp16's normal range: it then carries an absolute error of at most half the subnormal spacing, 2^-25, in
     scaled units.  Scales: weights of layer k by ws_k = 2^(13 - e), e the binade of the largest |w| of the layer
-    (``ani_hip.cpp``, wscale); forward activations by 2^4, backward gradients by 2^12.  So floor_o =
+    (``ani_hip_model.cpp``, wscale); forward activations by 2^4, backward gradients by 2^12.  So floor_o =
     2^-25 (sum_k |x_k| / ws + sum_k |w_ok| / a_scale).  bf16 has fp32's exponent range: floor = 0.
 * kacc(n): the fp32 accumulation of n terms, n = K * (number of split products: 6 or 3), plus the bias and the
   power-of-two rescale (exact).  The worst case is (n - 1) u; we use the probabilistic bound of Higham & Mary
@@ -81,7 +81,7 @@ def kacc(n):
 
 
 def _wscale(Ws):
-    """power of two of the fp16 weight planes of one layer (all members), as ani_hip.cpp computes it"""
+    """power of two of the fp16 weight planes of one layer (all members), as ani_hip_model.cpp computes it"""
     wmax = max(float(np.abs(W).max()) for W in Ws)
     if wmax == 0:
         return 1.0
