@@ -396,6 +396,23 @@ const char* ani_last_mlp_kernel(const ani_handle* h);
 int ani_debug_get(ani_handle* h, ani_debug_view* out);
 /* out[c], c < aev_active_length: column of the model's full AEV that column c of d_aev holds */
 int ani_debug_colmap(ani_handle* h, int* out);
+/* The handle's AEV stream tables (option "aev_stream_tables"), as they stand for the species present in the current epoch.
+ * species == 0: none (three or more species present, a model shape off the fast kernels, fp64).  Tuple index: one species: n;
+ * two: n0 (bound + 1) + n1, n_s = the centre's neighbours of (compact) species s inside Rca, each <= bound.  A descriptor is four
+ * ints {first word, stream length in slots, buckets, words reserved}; a tuple's words are words[first word + slot]:
+ *   backward: ia of the band's even row | ib << 8 | column position << 16 | bucket << 24 | triangular << 29 |
+ *             even row valid << 30 | odd row valid << 31          (ia, ib: positions in the centre's angular list)
+ *   forward:  ia | ib << 8 | bucket << 16 | valid << 24
+ * Any of the four output pointers may be NULL; the others receive 4 * tuples ints / words_bwd / words_fwd words. */
+typedef struct ani_stream_tables_view {
+  int32_t species, bound, tuples;
+  int32_t builds;        /* how often this handle has built tables (once per set of species present, not per neighbour list) */
+  int64_t words_bwd, words_fwd;
+  const void *d_words_bwd, *d_words_fwd;   /* device addresses, for identity checks */
+  double build_ms;       /* host time of the last build */
+} ani_stream_tables_view;
+int ani_debug_stream_tables(ani_handle* h, ani_stream_tables_view* view, int32_t* desc_bwd, uint32_t* words_bwd, int32_t* desc_fwd,
+                            uint32_t* words_fwd);
 /* the last force-armed model-deviation step's dg_m = dE_m/dAEV - mean (Hartree): member m's rows at d_parts + m * member_stride
  * elements, rows and columns laid out like d_gaev; float on an fp32 handle, double on an fp64 one (valid until the next step) */
 int ani_debug_deviation_parts(ani_handle* h, const void** d_parts, int64_t* member_stride);
@@ -444,6 +461,13 @@ int ani_debug_deviation_parts(ani_handle* h, const void** d_parts, int64_t* memb
  *     ani_compute_half, ani_compute_full_device at ago == 0) is CHECKED for this once per epoch (a hash sum over the entries
  *     between owned atoms, ~0.1 ms at 100 000 atoms); an epoch whose list fails runs with the scatter of every term, sets bit 8
  *     of error_flags and says so once on stderr.  Not used by the split step (ani_step_begin ...).
+ *   "aev_stream_tables" (default 1): which pair of a centre's angular neighbours a lane of the fast AEV kernels takes in a step, its
+ *     block of the AEV row and its padding depend on the centre's per-species neighbour counts alone.  With 1 the lanes read this
+ *     as one 32-bit word per step from tables kept per tuple of counts, built on the device when the set of species present is
+ *     installed (one or two species present, either count up to 32 -- up to the angular capacity for one species; 4.2 MB / 0.9 MB of device memory, capped at 8 MiB);
+ *     centres above the bound, layouts of three or more species, armed steps and the pyaev-compatible backward pass decode
+ *     arithmetically as with 0.  Same pairs in the same order: AEV rows bitwise equal, forces to the order of the atomic sums.
+ *     Takes effect at the next call.
  *   "aev_tickets_min" (default 40000): AEV launches over at least this many rows hand their rows to the waves by ticket (64 groups
  *     of workgroups, a counter each) instead of at a fixed stride; smaller launches keep the stride.  Same results.
  *   "mlp_fused_schedule" (default 1): which workgroup of the fused launch runs which tiles is decided on the host, once per

@@ -20,7 +20,7 @@ HARTREE2KCALMOL = 627.5094738898777
 
 EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani_use_num_models", "ani_num_species",
            "ani_aev_length", "ani_cutoff_radial", "ani_cutoff_angular", "ani_compute_full", "ani_compute_half",
-           "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_set_option", "ani_phase_timing", "ani_phase_times",
+           "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_debug_stream_tables", "ani_set_option", "ani_phase_timing", "ani_phase_times",
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
            "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
            "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts",
@@ -41,6 +41,13 @@ class DebugView(C.Structure):
     _fields_ = [("nlocal", C.c_int), ("ntotal", C.c_int), ("nrows", C.c_int), ("npairs", C.c_int64),
                 ("d_aev", C.c_void_p), ("d_gaev", C.c_void_p), ("d_row_of_centre", C.c_void_p),
                 ("species_count", C.c_int * 16), ("aev_stride", C.c_int), ("aev_active_length", C.c_int), ("error_flags", C.c_int)]
+
+
+class StreamTablesView(C.Structure):
+    """ani_stream_tables_view of include/ani_hip.h"""
+    _fields_ = [("species", C.c_int32), ("bound", C.c_int32), ("tuples", C.c_int32), ("builds", C.c_int32),
+                ("words_bwd", C.c_int64), ("words_fwd", C.c_int64), ("d_words_bwd", C.c_void_p), ("d_words_fwd", C.c_void_p),
+                ("build_ms", C.c_double)]
 
 
 class FireParams(C.Structure):
@@ -192,6 +199,7 @@ def lib():
         L.ani_debug_get.argtypes = [C.c_void_p, C.POINTER(DebugView)]
         L.ani_debug_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.ani_debug_colmap.argtypes = [C.c_void_p, C.c_void_p]
+        L.ani_debug_stream_tables.argtypes = [C.c_void_p, C.POINTER(StreamTablesView)] + [C.c_void_p] * 4
         L.ani_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.ani_last_mlp_kernel.argtypes = [C.c_void_p]
         L.ani_set_ghost_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -527,6 +535,20 @@ class ANI:
     def debug_read(self, d_ptr, shape, dtype) -> np.ndarray:
         out = np.empty(shape, dtype=dtype)
         self._check(self._lib.ani_debug_read(self._h, d_ptr, out.ctypes.data, out.nbytes))
+        return out
+
+    def stream_tables(self, contents: bool = True) -> dict:
+        """ani_debug_stream_tables: the view's fields and, with `contents`, desc_bwd / desc_fwd [tuples][4] (first word, stream
+        length, buckets, words reserved) and words_bwd / words_fwd (uint32) as host arrays; species == 0: the epoch has no tables."""
+        v = StreamTablesView()
+        self._check(self._lib.ani_debug_stream_tables(self._h, C.byref(v), None, None, None, None))
+        out = {n: getattr(v, n) for n, _ in StreamTablesView._fields_}
+        if contents and v.species:
+            db, df = np.zeros((v.tuples, 4), np.int32), np.zeros((v.tuples, 4), np.int32)
+            wb, wf = np.zeros(max(v.words_bwd, 1), np.uint32), np.zeros(max(v.words_fwd, 1), np.uint32)
+            self._check(self._lib.ani_debug_stream_tables(self._h, C.byref(v), db.ctypes.data, wb.ctypes.data, df.ctypes.data,
+                                                          wf.ctypes.data))
+            out.update(desc_bwd=db, words_bwd=wb[: v.words_bwd], desc_fwd=df, words_fwd=wf[: v.words_fwd])
         return out
 
     def colmap(self) -> np.ndarray:

@@ -107,6 +107,7 @@ struct Options {
   int aev_fused = 1;             // "aev_fused": 1 = neighbour compaction inside the forward AEV launch, 0 = its own kernel
   int aev_sym_radial = 1;        // "aev_symmetric_radial": see AevArgs::row_of_atom
   int aev_tickets_min = 40000;   // "aev_tickets_min": launches of fewer rows keep the fixed stride
+  int aev_stream_tables = 1;     // "aev_stream_tables": slot words of the angular pair streams from the handle's tables (StreamTab)
   int mlp_fused_sched = 1;   // "mlp_fused_schedule": 1 = static first-fit schedule of the fused launch, 0 = a counter
   int mlp_fused_halves = 1;  // "mlp_fused_halves": 1 = the schedule may cut straggler items in two (sixteen-row kernel),
                              // 0 = whole items only, 2 = every item as two halves (tests, measurements)
@@ -136,6 +137,20 @@ struct FusedState {
   int sched_key[4] = {-1, -1, -1, -1};   // what it was made for: total tiles, items per tile, problems, bins
   int sched_nitems = 0;      // entries of the schedule in sched (whole items + halves)
   DevBuf<float> gaev_parts;   // fused MLP with (tile, member) work items: every member's own dE/dAEV rows
+};
+
+// Stream tables of the AEV kernels (StreamTab in ani_kernels.h; build_stream_tables in ani_hip_model.cpp).  Lifetime: the species
+// map they were built for (mask); a re-neighbouring with the same species present leaves them alone.
+struct StreamTables {
+  int mask = -2;        // active_mask of the build; -2: never built
+  int S = 0, nt = 0;    // S = 0: this layout has no tables (three or more species, or a shape off the fast path)
+  int tuples = 0;
+  size_t nwords_b = 0, nwords_f = 0;
+  int builds = 0;       // how often the tables have been built (ani_debug_stream_tables)
+  double build_ms = 0;  // host time of the last build, synchronisations included
+  DevBuf<int4> desc_b, desc_f;
+  DevBuf<unsigned> words_b, words_f;
+  StreamTab view() const { return StreamTab{desc_b.p, words_b.p, desc_f.p, words_f.p, nt}; }
 };
 
 struct DevOut { double *member_energy, *atom_energy_dev, *member_dforce, *atom_force_dev, *summary; };   // model deviation: an armed step's outputs
@@ -236,6 +251,7 @@ struct ani_handle {
   int active_mask = -1;
   Options opt;
   FusedState fused;
+  StreamTables stab;
   Armed armed;
   MolFinder mol;
   Rdf rdf;
@@ -322,6 +338,7 @@ namespace ani_host __attribute__((visibility("hidden"))) {
 int check_args(ani_handle* h, int ntotal, int nlocal, long long npairs, int ago);   // ani_hip.cpp
 int upload_model(ani_handle* h);                                                     // ani_hip_model.cpp
 int specialize(ani_handle* h, int mask);
+int build_stream_tables(ani_handle* h, hipStream_t st);
 int compute_mlp(ani_handle* h, hipStream_t st);                                      // ani_hip_mlp.cpp
 void free_fused(ani_handle* h, int fi);
 const int* forced_fused_split(const char* env, int ntypes, const int* count, int* split);

@@ -203,11 +203,20 @@ AevArgs step_aev_args(ani_handle* h, const StepCtx& c, int rows) {
   return a;
 }
 
+// the handle's stream tables for a launch; NULL: arithmetic slot decode (option off, or no tables for the layout of the epoch)
+static const StreamTab* step_stream_tab(const ani_handle* h, StreamTab& view) {
+  if (!h->opt.aev_stream_tables || h->stab.S == 0 || h->stab.S != h->ap_run.S || h->stab.mask != h->active_mask) return nullptr;
+  view = h->stab.view();
+  return &view;
+}
+
 int step_compact_forward(ani_handle* h, const AevArgs& a, hipStream_t st) {
+  StreamTab tab_view;
+  const StreamTab* tab = step_stream_tab(h, tab_view);
   if (h->opt.aev_fused) {
     TraceRange tr("ani: neighbour compaction + AEV forward");
     if (h->timing.evt) HIP_TRY(h, hipEventRecord(h->timing.evt[5], st));   // the compaction phase is inside the forward launch
-    if (launch_aev_forward_fused(h->ap_run, a, h->max_numneigh, st)) {
+    if (launch_aev_forward_fused(h->ap_run, a, h->max_numneigh, st, tab)) {
       if (h->timing.evt) HIP_TRY(h, hipEventRecord(h->timing.evt[1], st));
       return ANI_OK;
     }
@@ -219,7 +228,7 @@ int step_compact_forward(ani_handle* h, const AevArgs& a, hipStream_t st) {
   if (h->timing.evt) HIP_TRY(h, hipEventRecord(h->timing.evt[5], st));
   {
     TraceRange tr("ani: AEV forward");
-    launch_aev_forward(h->ap_run, a, h->max_numneigh, st);
+    launch_aev_forward(h->ap_run, a, h->max_numneigh, st, tab);
   }
   if (h->timing.evt) HIP_TRY(h, hipEventRecord(h->timing.evt[1], st));
   return ANI_OK;
@@ -245,7 +254,8 @@ int step_backward(ani_handle* h, const StepCtx& c, const AevArgs& a, hipStream_t
       }
   }
   float* avir = static_cast<float*>(h->armed.av_acc);   // armed step: per-atom virial (ani_request_atom_virial)
-  const bool rep_done = launch_aev_backward(h->ap_run, a, h->max_numneigh, st, rt.on ? &rt : nullptr, avir) && rt.on;
+  StreamTab tab_view;
+  const bool rep_done = launch_aev_backward(h->ap_run, a, h->max_numneigh, st, rt.on ? &rt : nullptr, avir, step_stream_tab(h, tab_view)) && rt.on;
   if (m.has_rep && !rep_done) {
     RepArgs ra{};
     ra.row_info = h->row_info.p; ra.nrows = h->nrows; ra.jlist = h->jlist.p; ra.species = h->species.p;
@@ -510,6 +520,7 @@ void ani_destroy(ani_handle* h) {
   h->virial_acc.release(); h->aev.release(); h->gaev.release(); h->act.release(); h->aev64.release(); h->gaev64.release(); h->act64.release(); h->e_rows64.release(); h->fbuf64.release(); h->e_rows.release(); h->fbuf.release();
   for (int fi = 0; fi < 4; fi++) free_fused(h, fi);
   h->fused.counter.release(); h->fused.gaev_parts.release(); h->fused.sched.release();
+  h->stab.desc_b.release(); h->stab.desc_f.release(); h->stab.words_b.release(); h->stab.words_f.release();
   free_chain_plan(h->chain_plan);
   for (auto& e : h->timing.evt_pool) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);

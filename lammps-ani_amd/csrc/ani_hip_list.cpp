@@ -63,6 +63,8 @@ int rebuild(ani_handle* h, hipStream_t st) {
   {
     const int rcs = specialize(h, info[2 * kMaxSpecies + 3]);
     if (rcs) return rcs;
+    const int rct = build_stream_tables(h, st);   // once per species map, not per list
+    if (rct) return rct;
   }
   // A caller's list is checked for symmetry once per epoch (the symmetric radial collection relies on it); one that fails
   // runs with the scatter of every term, which is right for any list.  Said once.

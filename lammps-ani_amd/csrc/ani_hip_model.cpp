@@ -206,4 +206,46 @@ int specialize(ani_handle* h, int mask) {
   }
   return ANI_OK;
 }
+
+// Stream tables of the AEV kernels for the species map just installed (StreamTab in ani_kernels.h): built once per map -- a
+// re-neighbouring with the same species present returns at the first test.  Two passes per table: the lengths of every tuple's
+// stream (the kernels' own table builders on the device), an exclusive sum on the host, then the words.  A layout of three or more
+// species, or a shape off the fast path, has none.  The S = 2 bound is halved until both tables fit kStreamTabMaxBytes.
+int build_stream_tables(ani_handle* h, hipStream_t st) {
+  StreamTables& t = h->stab;
+  if (t.mask == h->active_mask) return ANI_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  t.mask = h->active_mask;
+  t.S = 0; t.nt = 0; t.tuples = 0; t.nwords_b = t.nwords_f = 0;
+  const AevParams& p = h->ap_run;
+  if (!h->use_single || !stream_tab_supported(p)) return ANI_OK;
+  std::vector<int4> db, df;
+  for (int nt = p.S == 1 ? kMaxAng : kStreamTabNT; nt >= 1; nt /= 2) {
+    const int n = stream_tab_tuples(p.S, nt);
+    HIP_TRY(h, t.desc_b.reserve(n));
+    HIP_TRY(h, t.desc_f.reserve(n));
+    launch_stream_table(p, nt, true, t.desc_b.p, nullptr, 0, st);
+    launch_stream_table(p, nt, false, t.desc_f.p, nullptr, 0, st);
+    db.resize(n); df.resize(n);
+    HIP_TRY(h, hipMemcpyAsync(db.data(), t.desc_b.p, sizeof(int4) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(df.data(), t.desc_f.p, sizeof(int4) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    size_t nb = 0, nf = 0;
+    for (int i = 0; i < n; i++) { db[i].x = (int)nb; nb += db[i].w; df[i].x = (int)nf; nf += df[i].w; }
+    if ((nb + nf) * sizeof(unsigned) + 2 * sizeof(int4) * (size_t)n > kStreamTabMaxBytes) continue;
+    HIP_TRY(h, t.words_b.reserve(std::max<size_t>(nb, 1)));
+    HIP_TRY(h, t.words_f.reserve(std::max<size_t>(nf, 1)));
+    HIP_TRY(h, hipMemcpyAsync(t.desc_b.p, db.data(), sizeof(int4) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t.desc_f.p, df.data(), sizeof(int4) * n, hipMemcpyHostToDevice, st));
+    launch_stream_table(p, nt, true, t.desc_b.p, t.words_b.p, 1, st);
+    launch_stream_table(p, nt, false, t.desc_f.p, t.words_f.p, 1, st);
+    HIP_TRY(h, hipStreamSynchronize(st));   // db / df leave scope; the build is timed whole
+    HIP_TRY(h, hipGetLastError());
+    t.S = p.S; t.nt = nt; t.tuples = n; t.nwords_b = nb; t.nwords_f = nf;
+    break;
+  }
+  t.builds++;
+  t.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return ANI_OK;
+}
 }  // namespace ani_host

@@ -40,6 +40,27 @@ int ani_debug_list(ani_handle* h, const int** d_numneigh, const int** d_nbr_off,
   return ANI_OK;
 }
 
+int ani_debug_stream_tables(ani_handle* h, ani_stream_tables_view* view, int32_t* desc_bwd, uint32_t* words_bwd, int32_t* desc_fwd,
+                            uint32_t* words_fwd) {
+  if (!h || !view) return ANI_ERR_ARG;
+  memset(view, 0, sizeof(*view));
+  const StreamTables& t = h->stab;
+  view->builds = t.builds;
+  view->build_ms = t.build_ms;
+  if (t.S == 0 || t.mask != h->active_mask) return ANI_OK;   // no tables for the layout of the epoch
+  view->species = t.S; view->bound = t.nt; view->tuples = t.tuples;
+  view->words_bwd = (int64_t)t.nwords_b; view->words_fwd = (int64_t)t.nwords_f;
+  view->d_words_bwd = t.words_b.p; view->d_words_fwd = t.words_f.p;
+  if (!desc_bwd && !words_bwd && !desc_fwd && !words_fwd) return ANI_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (desc_bwd) HIP_TRY(h, hipMemcpy(desc_bwd, t.desc_b.p, sizeof(int4) * t.tuples, hipMemcpyDeviceToHost));
+  if (desc_fwd) HIP_TRY(h, hipMemcpy(desc_fwd, t.desc_f.p, sizeof(int4) * t.tuples, hipMemcpyDeviceToHost));
+  if (words_bwd && t.nwords_b) HIP_TRY(h, hipMemcpy(words_bwd, t.words_b.p, sizeof(unsigned) * t.nwords_b, hipMemcpyDeviceToHost));
+  if (words_fwd && t.nwords_f) HIP_TRY(h, hipMemcpy(words_fwd, t.words_f.p, sizeof(unsigned) * t.nwords_f, hipMemcpyDeviceToHost));
+  return ANI_OK;
+}
+
 int ani_debug_colmap(ani_handle* h, int* out) {
   if (!h || !out) return ANI_ERR_ARG;
   for (int c = 0; c < h->ap_run.aev_len && c < (int)h->colmap.size(); c++) out[c] = h->colmap[c];
@@ -66,6 +87,7 @@ static const OptRow kOptionRows[] = {
     {"aev_symmetric_radial", &Options::aev_sym_radial, kFlag, {}, nullptr, kNothing},
     {"aev_tickets_min", &Options::aev_tickets_min, kRange, {0, kAny}, "aev_tickets_min must be >= 0", kNothing},
     {"aev_fused", &Options::aev_fused, kFlag, {}, nullptr, kNothing},
+    {"aev_stream_tables", &Options::aev_stream_tables, kFlag, {}, nullptr, kNothing},
     {"mlp_fused_gen", &Options::mlp_fused_gen, kRange, {0, 1}, "mlp_fused_gen must be 0 or 1", kSchedule},
     {"mlp_fused_rows", &Options::mlp_fused_rows, kSet, {0, 64, 128}, "mlp_fused_rows must be 0, 64 or 128", kSchedule},
     {"mlp_fused_halves", &Options::mlp_fused_halves, kRange, {0, 2}, "mlp_fused_halves must be 0, 1 or 2", kSchedule},

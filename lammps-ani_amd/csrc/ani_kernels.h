@@ -235,14 +235,41 @@ struct AevArgs {
   // next launch); NULL: fixed stride
   int* row_counter;
 };
+// Stream tables of the fast path (option "aev_stream_tables"): the angular pair streams of a centre -- which pair a lane of a step
+// takes, its bucket, its padding -- depend on the centre's per-species angular counts alone, so they are kept per tuple of counts
+// instead of being decoded by every lane of every step.  One table per stream (backward: build_pair_table / stream_pair_half;
+// forward: build_bucket_table / stream_pair), filled by the kernels' own device functions when the species map of an epoch is
+// installed.  Tuple index: S = 1: n, 0 <= n <= nt; S = 2: n0 (nt + 1) + n1, both <= nt.  A tuple's descriptor is
+// {first word, stream length, buckets, words reserved (the length rounded up to whole steps)}.
+//   backward word: ia of the band's even row | ib << 8 | column position c << 16 | bucket << 24 | triangular << 29 |
+//                  valid (even row) << 30 | valid (odd row) << 31; half h of the wave takes ia + h, pos = c - (triangular ? h : 0)
+//   forward word:  ia | ib << 8 | bucket << 16 | valid << 24
+// bucket: index among all S (S + 1) / 2 species pairs, outoff = radial_len + bucket NA NZ.
+struct StreamTab {
+  const int4* desc_b;
+  const unsigned* words_b;
+  const int4* desc_f;
+  const unsigned* words_f;
+  int nt;
+};
+constexpr int kStreamTabNT = 32;                         // S = 2: bound on either count
+constexpr size_t kStreamTabMaxBytes = 8u << 20;          // cap on a handle's two tables (nt is halved until they fit)
+// number of tuples for S species and bound nt (0: no tables for this S)
+inline int stream_tab_tuples(int S, int nt) { return S == 1 ? nt + 1 : (S == 2 ? (nt + 1) * (nt + 1) : 0); }
+// true if the model shape has stream tables at all (fast path, S <= 2)
+bool stream_tab_supported(const AevParams& p);
+// pass 0: desc[t] = {0, length, buckets, words reserved}; pass 1 (desc[t].x = first word): the words
+void launch_stream_table(const AevParams& p, int nt, bool backward, int4* d_desc, unsigned* d_words, int fill, hipStream_t st);
+
 // entries per row the compact lists need (0: the model shape takes the generic kernels, which keep no lists)
 int aev_compact_stride(const AevParams& p, int max_numneigh);
 // fast path only: screen every centre's candidate list into cl_hdr / cl_xyz / cl_j (once per step, before the forward pass)
 void launch_nbr_compact(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st);
 // max_numneigh (known at rebuild) sizes the per-centre LDS neighbour lists of the fast path
-void launch_aev_forward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st);
+// tab (all three launchers): the handle's stream tables, NULL = arithmetic slot decode everywhere
+void launch_aev_forward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const StreamTab* tab = nullptr);
 // compaction + forward as ONE launch (fast path, candidate lists of at most 256 entries); false: not applicable
-bool launch_aev_forward_fused(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st);
+bool launch_aev_forward_fused(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const StreamTab* tab = nullptr);
 // optional pairwise repulsion folded into the radial stage of the fast backward kernel (tables indexed by the compact
 // species of the run, like the AEV layout); `on` = 0: none.  Returns true if the kernel that ran applied it (the fast
 // path); false: the caller adds it with launch_repulsion.
@@ -258,7 +285,7 @@ struct RepTab {
 // avir: per-atom virial accumulator [ntotal][9] of an armed step (ani_request_atom_virial; floats, Hartree: avir[9 j + 3 a + b] +=
 // d_a g_b for every term whose force g lands on atom j, d = x_j - x_centre) -- NULL runs the unarmed kernels
 bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep = nullptr,
-                         float* avir = nullptr);
+                         float* avir = nullptr, const StreamTab* tab = nullptr);
 bool aev_fast_path(const AevParams& p, int max_numneigh);
 // rebuild time: stable sort of every centre's neighbour segment by neighbour species (jin -> jout)
 void launch_sort_jlist(const int* d_species, const int* d_nbr_off, const int* d_numneigh, const int* d_jin, int* d_jout,

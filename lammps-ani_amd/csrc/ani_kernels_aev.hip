@@ -29,6 +29,7 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "ani_kernels.h"
@@ -635,6 +636,85 @@ __device__ __forceinline__ void stream_pair_half(const FastLds& L, int nbk, int 
   ib = e0.w + b;
 }
 
+// ---- stream tables (StreamTab in ani_kernels.h): the two decodes above, done once per tuple of counts ----------------------
+// A centre's place in its stream: where its lane reads its slot words, how long the stream is, and the words already requested.
+// on = false: the centre decodes its slots arithmetically (no tables, or a count above their bound).
+struct StreamCur {
+  const unsigned* wp = nullptr;   // the stream's first word (wave-uniform: the lane adds its slot)
+  int total = 0;                  // stream length (slots)
+  unsigned w0 = 0, w1 = 0;        // the words of the next step and (backward) of the one after it
+  bool on = false;
+};
+// tuple index of a centre with n0 / n1 angular neighbours of species 0 / 1, -1 above the tables' bound.  The counts are compared
+// with the bound before they index anything.
+__device__ __forceinline__ int stream_tuple(const AevParams& p, const StreamTab& t, int n0, int n1) {
+  if (p.S == 1) return (unsigned)n0 <= (unsigned)t.nt ? n0 : -1;
+  return ((unsigned)n0 <= (unsigned)t.nt && (unsigned)n1 <= (unsigned)t.nt) ? n0 * (t.nt + 1) + n1 : -1;
+}
+// the descriptor through the scalar cache (as load_header_scalar), then the first word(s): STEP = slots per step (64 forward: one
+// word ahead; 32 backward, both half-waves on the same word: two ahead, the second step's word would otherwise be requested behind
+// the radial-only scatter in the in-order memory queue)
+template <int STEP>
+__device__ __forceinline__ StreamCur stream_begin(const int4* desc, const unsigned* words, int tix, int lane) {
+  StreamCur c;
+  if (tix < 0) return c;   // wave-uniform
+  int4 d;
+  asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(d) : "s"(desc + tix) : "memory");
+  c.on = true;
+  c.total = d.y;
+  c.wp = words + d.x;
+  if (d.y > 0) c.w0 = c.wp[lane & (STEP - 1)];
+  if (STEP == 32 && d.y > STEP) c.w1 = c.wp[STEP + (lane & 31)];
+  return c;
+}
+
+// Fills one tuple's run of a table with what the arithmetic decode yields: one wave per tuple, the counts of the tuple as the
+// group starts of an LDS slice that holds nothing else.
+template <int NA, int NZ, bool BWD>
+__global__ __launch_bounds__(64) void stream_table_kernel(AevParams p, int nt, int4* desc, unsigned* words, int fill) {
+  __shared__ int s_astart[24];
+  __shared__ int s_tb[kMaxBuckets * 8];
+  constexpr int STEP = BWD ? 32 : 64;
+  const int lane = threadIdx.x, t = blockIdx.x;
+  FastLds L{};
+  L.astart = s_astart;
+  L.tb = s_tb;
+  const int n0 = p.S == 1 ? t : t / (nt + 1), n1 = p.S == 1 ? 0 : t % (nt + 1);
+  if (lane <= p.S) s_astart[lane] = lane == 0 ? 0 : (lane == 1 ? n0 : n0 + n1);
+  wave_sync();
+  int nbk;
+  const int total = BWD ? build_pair_table<NA, NZ>(p, lane, L, nbk) : build_bucket_table<NA, NZ>(p, lane, L, nbk);
+  wave_sync();
+  const int reserved = (total + STEP - 1) / STEP * STEP;
+  if (!fill) {
+    if (lane == 0) desc[t] = make_int4(0, total, nbk, reserved);
+    return;
+  }
+  unsigned* out = words + desc[t].x;
+  for (int v = lane; v < reserved; v += 64) {
+    unsigned w;
+    if constexpr (BWD) {
+      int ia0, ib0, off0, pos0, ia1, ib1, off1, pos1;
+      bool v0, v1;
+      stream_pair_half(L, nbk, v, 0, ia0, ib0, off0, pos0, v0);
+      stream_pair_half(L, nbk, v, 1, ia1, ib1, off1, pos1, v1);
+      int e = 0;
+      for (int k = 1; k < nbk; k++)
+        if (v >= L.tb[8 * k]) e = k;
+      const int tri = L.tb[8 * e + 6], bk = (off0 - p.radial_len) / (NA * NZ);
+      w = (unsigned)ia0 | ((unsigned)ib0 << 8) | ((unsigned)pos0 << 16) | ((unsigned)bk << 24) | ((unsigned)(tri ? 1 : 0) << 29) |
+          ((unsigned)(v0 ? 1 : 0) << 30) | ((unsigned)(v1 ? 1 : 0) << 31);
+    } else {
+      int ia, ib, off;
+      bool valid;
+      stream_pair(L, nbk, v, ia, ib, off, valid);
+      const int bk = (off - p.radial_len) / (NA * NZ);
+      w = (unsigned)ia | ((unsigned)ib << 8) | ((unsigned)bk << 16) | ((unsigned)(valid ? 1 : 0) << 24);
+    }
+    out[v] = w;
+  }
+}
+
 // one add to a neighbour's fp64 gradient accumulator in LDS (FastLds::gd)
 __device__ __forceinline__ void gd_add(double* p, float v) { atomicAdd(p, (double)v); }
 // v + v[lane ^ OFF] without an LDS round trip: OFF = 1, 2, 4, 8 as DPP moves inside a row of 16 lanes, OFF = 16 / 32
@@ -664,22 +744,29 @@ __device__ __forceinline__ float xor_sum(float v) {
 
 // forward_compute: the AEV row of one centre from the wave's LDS lists (radial list grouped by species, angular list, group
 // starts) -- filled from the compact list by forward_centre, or straight from the candidate list by the fused kernel
-template <int NA, int NZ>
-__device__ __forceinline__ void forward_compute(const AevParams& p, const AevArgs& a, FastLds& L, int row, int lane BWD_STAMP_PARAMS);
+// TAB: the centre may come with its place in the forward stream table (sc.on); without it, and in the instantiations without tables,
+// the slots are decoded arithmetically
+template <int NA, int NZ, bool TAB>
+__device__ __forceinline__ void forward_compute(const AevParams& p, const AevArgs& a, FastLds& L, int row, int lane,
+                                                StreamCur sc BWD_STAMP_PARAMS);
 
-template <int NA, int NZ, int NCH>
+template <int NA, int NZ, int NCH, bool TAB>
 __device__ __forceinline__ void forward_centre(const AevParams& p, const AevArgs& a, FastLds& L, int row, const hdr_t& h,
-                                               const Loaded<NCH, false, 1>& pf, int lane BWD_STAMP_PARAMS) {
+                                               const Loaded<NCH, false, 1>& pf, int lane, const StreamTab& tab BWD_STAMP_PARAMS) {
+  StreamCur sc;
+  if constexpr (TAB)   // the header's count bytes -> tuple -> descriptor and first word, in flight during the unpack and the radial stage
+    sc = stream_begin<64>(tab.desc_f, tab.words_f, stream_tuple(p, tab, h[2] & 0xff, (h[2] >> 8) & 0xff), lane);
   for (int e = lane; e < (p.aev_stride >> 2); e += 64) reinterpret_cast<float4*>(L.row)[e] = make_float4(0, 0, 0, 0);
   int nrad, nang;
   unpack_lists<NCH>(p, a, row, h, pf, lane, L, nrad, nang);
   wave_sync();
   BWD_STAMP(2);   // unpack
-  forward_compute<NA, NZ>(p, a, L, row, lane BWD_STAMP_ARGS);
+  forward_compute<NA, NZ, TAB>(p, a, L, row, lane, sc BWD_STAMP_ARGS);
 }
 
-template <int NA, int NZ>
-__device__ __forceinline__ void forward_compute(const AevParams& p, const AevArgs& a, FastLds& L, int row, int lane BWD_STAMP_PARAMS) {
+template <int NA, int NZ, bool TAB>
+__device__ __forceinline__ void forward_compute(const AevParams& p, const AevArgs& a, FastLds& L, int row, int lane,
+                                                StreamCur sc BWD_STAMP_PARAMS) {
   constexpr int NR = 16, Q = 64 / NA;
 
   // ---- radial: per species group, lanes = (slot q, shift k) ----
@@ -709,9 +796,15 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
 
   BWD_STAMP(3);   // radial
   // ---- angular ----
-  int nbk;
-  const int total = build_bucket_table<NA, NZ>(p, lane, L, nbk);
-  wave_sync();
+  int nbk = 0, total;
+  bool tabbed = false;   // wave-uniform: this centre's slots come from the stream table
+  if constexpr (TAB) tabbed = sc.on;
+  if (tabbed) {
+    total = sc.total;
+  } else {
+    total = build_bucket_table<NA, NZ>(p, lane, L, nbk);
+    wave_sync();
+  }
   BWD_STAMP(4);   // bucket table
   float acc[NZ];
 #pragma unroll
@@ -761,7 +854,16 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
     {
       int ia, ib;
       bool valid;
-      stream_pair(L, nbk, base + lane, ia, ib, outoff, valid);
+      if (tabbed) {   // the word requested a step ago; the next step's leaves now
+        const unsigned w = sc.w0;
+        if (base + 64 < total) sc.w0 = sc.wp[base + 64 + lane];
+        ia = w & 0xff;
+        ib = (w >> 8) & 0xff;
+        outoff = p.radial_len + (int)((w >> 16) & 0xff) * (NA * NZ);
+        valid = (w >> 24) & 1;
+      } else {
+        stream_pair(L, nbk, base + lane, ia, ib, outoff, valid);
+      }
       const float4 A = L.ad[ia], B = L.ad[ib];
       const float dot = A.x * B.x + A.y * B.y + A.z * B.z;
       const float cth = 0.95f * dot * frcp(fmaxf(A.w * B.w, 1e-10f));
@@ -894,8 +996,19 @@ __device__ __forceinline__ void forward_compute(const AevParams& p, const AevArg
   }                                                                                                       \
   ANI_TICKETS_END(KW)
 
-template <int NA, int NZ, int NCH>
-__global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(AevParams p, AevArgs a, int cap, int rowf) {
+// TBP: empty, or StreamTab for the instantiations that take slot words from the stream tables -- a parameter pack, so that the kernels
+// without tables keep their argument list, and with it their instruction stream, exactly as it was
+template <typename... TBP>
+__device__ __forceinline__ StreamTab tab_of(const TBP&... tbp) {
+  StreamTab t{};
+  if constexpr (sizeof...(TBP) > 0) t = (tbp, ...);
+  return t;
+}
+
+template <int NA, int NZ, int NCH, typename... TBP>
+__global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(AevParams p, AevArgs a, int cap, int rowf, TBP... tbp) {
+  constexpr bool TAB = sizeof...(TBP) > 0;
+  const StreamTab tab = tab_of(tbp...);
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   FastLds L = carve<NA, NZ>(reinterpret_cast<float*>(smem4) + wave * fast_wave_floats_row(cap, false, rowf, p.S), cap, false, rowf);
@@ -911,7 +1024,7 @@ __global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(Ae
     Loaded<NCH, false, 1> cur;
     load_lists(p, a, row, hdr_nrad(hc), hdr_nang(hc), lane, cur);
     BWD_STAMP(1);
-    forward_centre<NA, NZ, NCH>(p, a, L, row, hc, cur, lane, stamp_prev, stamp_acc);
+    forward_centre<NA, NZ, NCH, TAB>(p, a, L, row, hc, cur, lane, tab, stamp_prev, stamp_acc);
     stamp_acc[7] += 1;
   }
   if (wave == 0 && lane == 0) {
@@ -919,7 +1032,7 @@ __global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(Ae
     atomicAdd(&g_bwd_stamps[24], stamp_acc[7]);
   }
 #else
-  ANI_PERSISTENT_LOOP(kWaves, NCH, false, 1, (forward_centre<NA, NZ, NCH>(p, a, L, row, hc, cur, lane)))
+  ANI_PERSISTENT_LOOP(kWaves, NCH, false, 1, (forward_centre<NA, NZ, NCH, TAB>(p, a, L, row, hc, cur, lane, tab)))
 #endif
 }
 
@@ -932,8 +1045,10 @@ __global__ __launch_bounds__(64 * kWaves, kFwdMinWaves) void aev_forward_fast(Ae
 // screened candidates (no compact list read back, no unpack from it), and the compact list and its header are still
 // written -- the backward kernel starts from them.  Candidate lists longer than 64 NCHC entries, or AEV shapes off the fast
 // path, take the two kernels.
-template <int NA, int NZ, int NCHC>
-__global__ __launch_bounds__(64 * kWaves, kFusedMinWaves) void aev_forward_fused(AevParams p, AevArgs a, int cap, int rowf) {
+template <int NA, int NZ, int NCHC, typename... TBP>
+__global__ __launch_bounds__(64 * kWaves, kFusedMinWaves) void aev_forward_fused(AevParams p, AevArgs a, int cap, int rowf, TBP... tbp) {
+  constexpr bool TAB = sizeof...(TBP) > 0;
+  const StreamTab tab = tab_of(tbp...);
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   FastLds L = carve<NA, NZ>(reinterpret_cast<float*>(smem4) + wave * fast_wave_floats_row(cap, false, rowf, p.S), cap, false, rowf);
@@ -991,6 +1106,14 @@ __global__ __launch_bounds__(64 * kWaves, kFusedMinWaves) void aev_forward_fused
         pos[c] = (in_a && pA < kMaxAng) ? pA : ((in_2 && p2 < cap2) ? kMaxAng + p2 : -1);
       }
     }
+    // stream table: the screened counts (lanes 0 and 1) -> tuple -> descriptor and first slot word, requested here, in front of the
+    // centre's stores in the in-order memory queue; a row that is skipped below (over) is above the tables' bound as well
+    StreamCur sc;
+    if constexpr (TAB) {
+      const int c0 = __builtin_amdgcn_readlane(cc, 0) & 0xffff, c1 = __builtin_amdgcn_readlane(cc, 1) & 0xffff;
+      const bool live = inf.x >= 0 && !(nA > kMaxAng || nR > cap2 || nA + nR > cap);
+      sc = stream_begin<64>(tab.desc_f, tab.words_f, live ? stream_tuple(p, tab, c0, c1) : -1, lane);
+    }
     // the next centre's candidate indices are in registers before this centre's stores enter the (in-order) memory queue
 #pragma unroll
     for (int c = 0; c < NCHC; c++) touch(jj1[c]);
@@ -1041,9 +1164,9 @@ __global__ __launch_bounds__(64 * kWaves, kFusedMinWaves) void aev_forward_fused
       wave_sync();
 #ifdef ABLB_STAMPS
       unsigned long long stamp_prev = 0, stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      forward_compute<NA, NZ>(p, a, L, row, lane, stamp_prev, stamp_acc);
+      forward_compute<NA, NZ, TAB>(p, a, L, row, lane, sc, stamp_prev, stamp_acc);
 #else
-      forward_compute<NA, NZ>(p, a, L, row, lane);
+      forward_compute<NA, NZ, TAB>(p, a, L, row, lane, sc);
 #endif
     }
     info = info1;
@@ -1082,10 +1205,11 @@ __device__ __forceinline__ void scatter_atom_virial(float* __restrict__ avir, co
 }
 
 // AV: per-atom virial into avir[ntotal][9] (see scatter_atom_virial); vt: [3*64] LDS staging of the radial-only displacements
-template <int NA, int NZ, int NCH, int GR, bool VIR, bool AV, typename PF>
+// TAB, sc: the centre's place in the backward stream table (sc.on), requested by the caller with the centre's lists
+template <int NA, int NZ, int NCH, int GR, bool VIR, bool AV, bool TAB, typename PF>
 __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArgs& a, FastLds& L, int row, const hdr_t h,
                                                 const Loaded<NCH, true, GR> pf, int lane, float (&wv)[9],
-                                                const RepTab& rep, float* __restrict__ avir, float* vt, float& er,
+                                                const RepTab& rep, float* __restrict__ avir, float* vt, float& er, StreamCur sc,
                                                 PF&& before_final_scatter BWD_STAMP_PARAMS) {
   constexpr int NR = 16;
   const int centre = h[0];
@@ -1288,15 +1412,34 @@ __device__ __forceinline__ void backward_centre(const AevParams& p, const AevArg
   // consecutive lanes (a run): its gradient is summed over the run by a segmented scan inside each 16-lane DPP row -- level d
   // adds the value d lanes down if that lane belongs to the same run -- and the last lane of the run in its DPP row adds the
   // partial sum to the neighbour's LDS accumulator.  The COLUMN neighbour's gradient: one LDS add per lane.
-  int nbk;
-  const int total_pairs = build_pair_table<NA, NZ>(p, lane, L, nbk);
-  wave_sync();
+  int nbk = 0, total_pairs;
+  bool tabbed = false;   // wave-uniform: this centre's slots come from the stream table
+  if constexpr (TAB) tabbed = sc.on;
+  if (tabbed) {
+    total_pairs = sc.total;
+  } else {
+    total_pairs = build_pair_table<NA, NZ>(p, lane, L, nbk);
+    wave_sync();
+  }
   BWD_STAMP(3);   // pair table
   const float cA = -p.EtaA * kLog2e;
   for (int base = 0; base < total_pairs; base += 32) {
     int ia, ib, outoff, pos;
     bool valid;
-    stream_pair_half(L, nbk, base + (lane & 31), lane >> 5, ia, ib, outoff, pos, valid);
+    if (tabbed) {   // the word requested two steps ago; the one of the step after the next leaves now
+      const unsigned w = sc.w0;
+      sc.w0 = sc.w1;
+      if (base + 64 < total_pairs) sc.w1 = sc.wp[base + 64 + (lane & 31)];
+      const int hh = lane >> 5;
+      valid = (w >> (30 + hh)) & 1;
+      const int up = valid ? hh : 0;   // an idle upper half stays on the even row's pair: a harmless geometry
+      ia = (int)(w & 0xff) + up;
+      ib = (w >> 8) & 0xff;
+      pos = valid ? (int)((w >> 16) & 0xff) - (int)((w >> 29) & (unsigned)up) : 0;
+      outoff = p.radial_len + (int)((w >> 24) & 0x1f) * (NA * NZ);
+    } else {
+      stream_pair_half(L, nbk, base + (lane & 31), lane >> 5, ia, ib, outoff, pos, valid);
+    }
     const float4 A = L.ad[ia], B = L.ad[ib];
     const float inv_ra = frcp(A.w), inv_rb = frcp(B.w);
     const float inv_rr = inv_ra * inv_rb;
@@ -1411,16 +1554,30 @@ __host__ __device__ constexpr int bwd_wave_floats(int cap, int rowf, int S, bool
 }
 static_assert((fast_wave_floats(0, true) + 3 * 64) * 4 * kWavesB <= 160 * 1024, "armed backward LDS");
 
-// AVP: empty, or float* for the armed instantiation (per-atom virial accumulator) -- a parameter pack, so that the unarmed kernels keep
-// their argument list, and with it their instruction stream, exactly as it was
+// AVP: empty, float* for the armed instantiation (per-atom virial accumulator), StreamTab for the ones with stream tables, or both
+// (StreamTab first) -- a parameter pack, so that the unarmed kernels without tables keep their argument list, and with it their
+// instruction stream, exactly as it was
+__device__ __forceinline__ void take_extra(StreamTab&, float*&) {}
+template <typename... R>
+__device__ __forceinline__ void take_extra(StreamTab& t, float*& av, float* x, R... r) { av = x; take_extra(t, av, r...); }
+template <typename... R>
+__device__ __forceinline__ void take_extra(StreamTab& t, float*& av, StreamTab x, R... r) { t = x; take_extra(t, av, r...); }
+template <typename T, typename... P> constexpr bool pack_has = (std::is_same<T, P>::value || ...);
+
 template <int NA, int NZ, int NCH, int GR, bool VIR, typename... AVP>
 __global__ __launch_bounds__(64 * kWavesB, kBwdMinWaves) void aev_backward_fast(AevParams p, AevArgs a, int cap, int rowf, RepTab rep,
                                                                                 AVP... avp) {
-  constexpr bool AV = sizeof...(AVP) > 0;
+  constexpr bool AV = pack_has<float*, AVP...>, TAB = pack_has<StreamTab, AVP...>;
   float* avir = nullptr;
-  if constexpr (AV) avir = (avp, ...);
+  StreamTab tab{};
+  take_extra(tab, avir, avp...);
   extern __shared__ float4 smem4[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // the centre's place in the backward stream table, from the count bytes of its header (scalar)
+  auto stream_of = [&](const hdr_t& hx) -> StreamCur {
+    if constexpr (TAB) return stream_begin<32>(tab.desc_b, tab.words_b, stream_tuple(p, tab, hx[2] & 0xff, (hx[2] >> 8) & 0xff), lane);
+    else return StreamCur{};
+  };
   float* wbase = reinterpret_cast<float*>(smem4) + wave * bwd_wave_floats(cap, rowf, p.S, AV);
   FastLds L = carve<NA, NZ>(wbase, cap, true, rowf);
   float* vt = AV ? wbase + fast_wave_floats_row(cap, true, rowf, p.S) : nullptr;
@@ -1442,7 +1599,8 @@ __global__ __launch_bounds__(64 * kWavesB, kBwdMinWaves) void aev_backward_fast(
 #else
     BWD_STAMP(1);
 #endif
-    backward_centre<NA, NZ, NCH, GR, VIR, AV>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, [] {}, stamp_prev, stamp_acc);
+    backward_centre<NA, NZ, NCH, GR, VIR, AV, TAB>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, stream_of(hc), [] {}, stamp_prev,
+                                                   stamp_acc);
     stamp_acc[6] += 1;
   }
   if (wave == 0 && lane == 0) {
@@ -1465,6 +1623,7 @@ __global__ __launch_bounds__(64 * kWavesB, kBwdMinWaves) void aev_backward_fast(
   bool have = false;   // hc / cur already hold the centre of ticket k (requested in front of the previous centre's final scatter)
   hdr_t hc;
   Loaded<NCH, true, GR> cur;
+  StreamCur sc;   // travels with hc / cur
   while (k < kstop) {
     ANI_TICKET_DRAW(tk_tn)
     const int kk = rank_of(k);
@@ -1472,18 +1631,24 @@ __global__ __launch_bounds__(64 * kWavesB, kBwdMinWaves) void aev_backward_fast(
     const bool in_range = kk < a.kcount;
     if (!have) {
       hc = load_header_scalar(a, row);
-      if (hc[0] >= 0 && in_range) load_lists(p, a, row, hdr_nrad(hc), hdr_nang(hc), lane, cur);
+      if (hc[0] >= 0 && in_range) {
+        load_lists(p, a, row, hdr_nrad(hc), hdr_nang(hc), lane, cur);
+        sc = stream_of(hc);
+      }
     }
     have = false;
     ANI_TICKET_TAKE(tk_k2)
     if (hc[0] >= 0 && in_range) {
       // header and lists go in by value: the hook overwrites hc / cur with the next centre's while this one finishes
-      backward_centre<NA, NZ, NCH, GR, VIR, AV>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, [&]() {
+      backward_centre<NA, NZ, NCH, GR, VIR, AV, TAB>(p, a, L, row, hc, cur, lane, wv, rep, avir, vt, er, sc, [&]() {
         const int kk1 = rank_of(k1);
         if (k1 < kstop && kk1 < a.kcount) {   // wave-uniform
           const int row1 = row_of(kk1);
           hc = load_header_scalar(a, row1);
-          if (hc[0] >= 0) load_lists(p, a, row1, hdr_nrad(hc), hdr_nang(hc), lane, cur);
+          if (hc[0] >= 0) {
+            load_lists(p, a, row1, hdr_nrad(hc), hdr_nang(hc), lane, cur);
+            sc = stream_of(hc);   // first slot words of the next centre: in front of this centre's atomics, like its lists
+          }
           have = true;
         }
       });
@@ -1861,7 +2026,26 @@ void launch_nbr_compact(const AevParams& p, const AevArgs& a, int max_numneigh, 
   else go(nbr_compact_kernel<4>);
 }
 
-void launch_aev_forward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st) {
+bool stream_tab_supported(const AevParams& p) { return fast_kind(p) != 0 && (p.S == 1 || p.S == 2); }
+
+void launch_stream_table(const AevParams& p, int nt, bool backward, int4* d_desc, unsigned* d_words, int fill, hipStream_t st) {
+  const int n = stream_tab_tuples(p.S, nt);
+  if (n <= 0 || !stream_tab_supported(p)) return;
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n), dim3(64), 0, st, p, nt, d_desc, d_words, fill); };
+  const bool k1 = fast_kind(p) == 1;
+  if (k1 && backward) go(stream_table_kernel<8, 4, true>);
+  else if (k1) go(stream_table_kernel<8, 4, false>);
+  else if (backward) go(stream_table_kernel<4, 8, true>);
+  else go(stream_table_kernel<4, 8, false>);
+}
+
+// tables only where they were built for this layout: one or two species
+static const StreamTab* usable_tab(const AevParams& p, const StreamTab* tab) {
+  return (tab && tab->desc_b && tab->desc_f && (p.S == 1 || p.S == 2)) ? tab : nullptr;
+}
+
+void launch_aev_forward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const StreamTab* tab) {
+  tab = usable_tab(p, tab);
   if (a.nrows <= 0) return;
   const dim3 grid((a.nrows + kWaves - 1) / kWaves), block(64 * kWaves);
   if (aev_fast_path(p, max_numneigh)) {
@@ -1872,37 +2056,46 @@ void launch_aev_forward(const AevParams& p, const AevArgs& a, int max_numneigh, 
     // 64-entry chunks of the radial-only stream prefetched per centre: 1 with the radial screen on (more than 64
     // neighbours between Rca and Rcr are loaded in place), 3 in pyaev mode where every candidate stays
     const bool k1 = fast_kind(p) == 1, n2 = !p.compat;
-    if (k1 && n2) launch_fast(aev_forward_fast<8, 4, 1>, p, a, kWaves, lds, cap, rowf, st);
-    else if (k1) launch_fast(aev_forward_fast<8, 4, 3>, p, a, kWaves, lds, cap, rowf, st);
-    else if (n2) launch_fast(aev_forward_fast<4, 8, 1>, p, a, kWaves, lds, cap, rowf, st);
-    else launch_fast(aev_forward_fast<4, 8, 3>, p, a, kWaves, lds, cap, rowf, st);
+#define ANI_FWD_CASE(K, ...)                                                                       \
+  do {                                                                                             \
+    if (tab) launch_fast(K<__VA_ARGS__, StreamTab>, p, a, kWaves, lds, cap, rowf, st, *tab);       \
+    else launch_fast(K<__VA_ARGS__>, p, a, kWaves, lds, cap, rowf, st);                            \
+  } while (0)
+    if (k1 && n2) ANI_FWD_CASE(aev_forward_fast, 8, 4, 1);
+    else if (k1) ANI_FWD_CASE(aev_forward_fast, 8, 4, 3);
+    else if (n2) ANI_FWD_CASE(aev_forward_fast, 4, 8, 1);
+    else ANI_FWD_CASE(aev_forward_fast, 4, 8, 3);
   } else {
     hipLaunchKernelGGL(aev_forward_generic, grid, block, 0, st, p, a);
   }
 }
 
 // compaction + forward in one launch; false: not applicable (the caller launches the two kernels)
-bool launch_aev_forward_fused(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st) {
+bool launch_aev_forward_fused(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const StreamTab* tab) {
   if (a.nrows <= 0 || a.kcount <= 0 || !aev_fast_path(p, max_numneigh) || max_numneigh > 256) return false;
+  tab = usable_tab(p, tab);
   const int cap = radial_cap(p, max_numneigh);
   const int rowf = (p.aev_stride + 63) / 64 * 64;
   const size_t lds = (size_t)fast_wave_floats_row(cap, false, rowf, p.S) * 4 * kWaves;
   const bool k1 = fast_kind(p) == 1;
   const int nch = max_numneigh <= 128 ? 2 : (max_numneigh <= 192 ? 3 : 4);
   if (k1) {
-    if (nch == 2) launch_fast(aev_forward_fused<8, 4, 2>, p, a, kWaves, lds, cap, rowf, st);
-    else if (nch == 3) launch_fast(aev_forward_fused<8, 4, 3>, p, a, kWaves, lds, cap, rowf, st);
-    else launch_fast(aev_forward_fused<8, 4, 4>, p, a, kWaves, lds, cap, rowf, st);
+    if (nch == 2) ANI_FWD_CASE(aev_forward_fused, 8, 4, 2);
+    else if (nch == 3) ANI_FWD_CASE(aev_forward_fused, 8, 4, 3);
+    else ANI_FWD_CASE(aev_forward_fused, 8, 4, 4);
   } else {
-    if (nch == 2) launch_fast(aev_forward_fused<4, 8, 2>, p, a, kWaves, lds, cap, rowf, st);
-    else if (nch == 3) launch_fast(aev_forward_fused<4, 8, 3>, p, a, kWaves, lds, cap, rowf, st);
-    else launch_fast(aev_forward_fused<4, 8, 4>, p, a, kWaves, lds, cap, rowf, st);
+    if (nch == 2) ANI_FWD_CASE(aev_forward_fused, 4, 8, 2);
+    else if (nch == 3) ANI_FWD_CASE(aev_forward_fused, 4, 8, 3);
+    else ANI_FWD_CASE(aev_forward_fused, 4, 8, 4);
   }
+#undef ANI_FWD_CASE
   return true;
 }
 
-bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep, float* avir) {
+bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh, hipStream_t st, const RepTab* rep, float* avir,
+                         const StreamTab* tab) {
   if (a.nrows <= 0) return true;
+  tab = usable_tab(p, tab);
   RepTab rt{};
   if (rep) rt = *rep;
   const dim3 grid((a.nrows + kWaves - 1) / kWaves), block(64 * kWaves);
@@ -1915,6 +2108,13 @@ bool launch_aev_backward(const AevParams& p, const AevArgs& a, int max_numneigh,
     // armed (per-atom virial): its own instantiations, always with the global virial; the unarmed kernels stay what they were
 #define ANI_BWD_CASE(NA, NZ, NCH, GR)                                                                              \
   do {                                                                                                             \
+    if constexpr (GR == 1 && NCH == 1) {   /* what a layout of one or two species runs with the radial screen on */              \
+      if (tab && !avir) {                                                                                                         \
+        if (a.virial) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true, StreamTab>, p, a, kWavesB, lds, cap, rowf, st, rt, *tab);   \
+        else launch_fast(aev_backward_fast<NA, NZ, NCH, GR, false, StreamTab>, p, a, kWavesB, lds, cap, rowf, st, rt, *tab);           \
+        break;                                                                                                                    \
+      }                                                                                                                           \
+    }                                                                                                                             \
     if (avir) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true, float*>, p, a, kWavesB, lds, cap, rowf, st, rt, avir);  \
     else if (a.virial) launch_fast(aev_backward_fast<NA, NZ, NCH, GR, true>, p, a, kWavesB, lds, cap, rowf, st, rt);      \
     else launch_fast(aev_backward_fast<NA, NZ, NCH, GR, false>, p, a, kWavesB, lds, cap, rowf, st, rt);                   \
