@@ -39,7 +39,10 @@ typedef struct ani_handle ani_handle;
  * (src/ani_csrc/ani.h:31-36, src/ani_csrc/ani.cpp:35-97).
  *   model_file      flat model file (lammps-ani_amd/model_file.py), not a TorchScript archive; an optional trailing block
  *                   carries the tables of the pairwise repulsion the reference attaches to reactive models
- *                   (models/ani_models.py:50-53), which is then added to energy, forces and virial
+ *                   (models/ani_models.py:50-53), which is then added to energy, forces and virial.  With use_single the
+ *                   term is folded into the fast AEV backward kernel when at most 8 species are present and the block's
+ *                   cutoff does not exceed Rcr (or use_cuaev = 0, where every list entry stays live); otherwise a
+ *                   stand-alone kernel adds it over the whole list (ani_last_repulsion_kernel names the one that ran)
  *   local_rank      HIP device ordinal (the reference maps node-local rank % device count, src/pair_ani.cpp:255-283);
  *                   -1 = cpu is refused
  *   use_num_models  first n ensemble members, -1 = all (models/lammps_ani.py:332-343)
@@ -393,6 +396,10 @@ int ani_host_unregister(const void* p);
 /* name of the kernel that ran the MLP of the last step ("mlp_fused<3>", "mlp_chain", "mlp_pipeline", "gemm_grouped ..."): what a
  * profile's kernel statistics list it under (bench.py's roofline block names it) */
 const char* ani_last_mlp_kernel(const ani_handle* h);
+/* name of the kernel that added the pairwise repulsion of the last step: "aev_backward_fast" (folded into the fast AEV backward
+ * kernel), "repulsion_kernel<float>" or "repulsion_kernel<double>" (the stand-alone kernel of either precision); "" for a model
+ * without the block and before the first step */
+const char* ani_last_repulsion_kernel(const ani_handle* h);
 int ani_debug_get(ani_handle* h, ani_debug_view* out);
 /* out[c], c < aev_active_length: column of the model's full AEV that column c of d_aev holds */
 int ani_debug_colmap(ani_handle* h, int* out);

@@ -22,7 +22,7 @@ EXPORTS = ["ani_create", "ani_destroy", "ani_last_error", "ani_num_models", "ani
            "ani_aev_length", "ani_cutoff_radial", "ani_cutoff_angular", "ani_compute_full", "ani_compute_half",
            "ani_compute_full_device", "ani_build_list_device", "ani_build_list", "ani_debug_list", "ani_debug_get", "ani_debug_read", "ani_debug_colmap", "ani_debug_stream_tables", "ani_set_option", "ani_phase_timing", "ani_phase_times",
            "ani_trace_push", "ani_trace_pop", "ani_trace_mark", "ani_step_begin", "ani_step_ghosts_ready", "ani_step_finish",
-           "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
+           "ani_debug_fused_stamps", "ani_attach_comm", "ani_debug_fused_schedule", "ani_debug_fused_schedule_halves", "ani_last_mlp_kernel", "ani_last_repulsion_kernel", "ani_host_register", "ani_host_unregister", "ani_set_ghost_fold", "ani_stage_ghost_fold",
            "ani_request_atom_virial", "ani_request_model_deviation", "ani_debug_deviation_parts",
            "ani_set_bond_table", "ani_find_molecules_device", "ani_find_molecules", "ani_species_symbol",
            "ani_rdf_configure", "ani_rdf_accumulate_device", "ani_rdf_accumulate", "ani_rdf_read"]
@@ -221,6 +221,8 @@ def lib():
         L.ani_host_register.argtypes = [C.c_void_p, C.c_size_t]
         L.ani_host_unregister.argtypes = [C.c_void_p]
         L.ani_last_mlp_kernel.restype = C.c_char_p
+        L.ani_last_repulsion_kernel.argtypes = [C.c_void_p]
+        L.ani_last_repulsion_kernel.restype = C.c_char_p
         # include/ani_md.h: kernels of the LAMMPS-free timestep loop (not part of the drop-in boundary)
         L.ani_md_initial_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
@@ -681,6 +683,10 @@ class ANI:
 
     def last_mlp_kernel(self) -> str:
         return self._lib.ani_last_mlp_kernel(self._h).decode()
+
+    def last_repulsion_kernel(self) -> str:
+        """ani_last_repulsion_kernel: "aev_backward_fast", "repulsion_kernel<float>", "repulsion_kernel<double>", or "" (no block / no step yet)"""
+        return self._lib.ani_last_repulsion_kernel(self._h).decode()
 
     def cutoffs(self):
         """(Rcr, Rca) of the model"""

@@ -259,6 +259,7 @@ struct ani_handle {
   HostStaging host;
   PhaseTiming timing;
   const char* last_mlp_kernel = "";   // ani_last_mlp_kernel: the kernel that ran the MLP of the last step
+  const char* last_rep_kernel = "";   // ani_last_repulsion_kernel: the kernel that added the repulsion of the last step
   ChainPlan chain_plan;
   std::vector<int> colmap;  // ap_run column -> ap column
   int device = 0;

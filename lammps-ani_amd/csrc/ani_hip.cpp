@@ -113,6 +113,7 @@ int run_step64(ani_handle* h, const double* d_x, int eflag_atom, int vflag, doub
     ra.pos = d_x; ra.fbuf = h->fbuf64.p; ra.virial = vflag ? h->virial_acc.p : nullptr; ra.erep = h->erep.p;
     ra.tables = h->rep_tables.p; ra.S = m.S; ra.nslots = kVirialSlots; ra.vslots = 1; ra.cutoff = m.rep_cut;
     launch_repulsion(ra, true, st, h->armed.av_acc);
+    h->last_rep_kernel = "repulsion_kernel<double>";
   }
   Sae64 sae{};
   for (int s = 0; s < m.S; s++) sae.v[s] = m.sae[s];
@@ -234,12 +235,20 @@ int step_compact_forward(ani_handle* h, const AevArgs& a, hipStream_t st) {
   return ANI_OK;
 }
 
+// The repulsion is folded into the radial stage of the fast AEV backward kernel: at most 8 species present (its tables), and
+// every pair inside the block's cutoff among the entries that stage walks -- the compacted radial list holds r <= Rcr, so
+// rep_cut <= Rcr, or the pyaev mode, which keeps every candidate.  Otherwise the stand-alone kernel adds the term.
+bool rep_folded(const ani_handle* h) {
+  const HostModel& m = h->model;
+  return m.has_rep && h->ap_run.S <= 8 && (m.rep_cut <= m.Rcr || h->ap_run.compat);
+}
+
 int step_backward(ani_handle* h, const StepCtx& c, const AevArgs& a, hipStream_t st) {
   const HostModel& m = h->model;
   // the fast backward kernel applies the repulsion in its radial stage (tables by compact species, like the AEV layout);
   // the generic kernel does not, and then the stand-alone kernel adds it
   RepTab rt{};
-  if (m.has_rep && h->ap_run.S <= 8) {
+  if (rep_folded(h)) {
     rt.on = 1; rt.cutoff = (float)m.rep_cut; rt.erep = h->erep.p; rt.x64 = c.d_x;
     std::vector<int> act;
     for (int s = 0; s < m.S; s++) if (h->active_mask & (1 << s)) act.push_back(s);
@@ -256,6 +265,7 @@ int step_backward(ani_handle* h, const StepCtx& c, const AevArgs& a, hipStream_t
   float* avir = static_cast<float*>(h->armed.av_acc);   // armed step: per-atom virial (ani_request_atom_virial)
   StreamTab tab_view;
   const bool rep_done = launch_aev_backward(h->ap_run, a, h->max_numneigh, st, rt.on ? &rt : nullptr, avir, step_stream_tab(h, tab_view)) && rt.on;
+  if (m.has_rep) h->last_rep_kernel = rep_done ? "aev_backward_fast" : "repulsion_kernel<float>";
   if (m.has_rep && !rep_done) {
     RepArgs ra{};
     ra.row_info = h->row_info.p; ra.nrows = h->nrows; ra.jlist = h->jlist.p; ra.species = h->species.p;
@@ -326,7 +336,7 @@ int run_step(ani_handle* h, const double* d_x, int eflag_atom, int vflag, double
   return ANI_OK;
 }
 
-bool split_supported(const ani_handle* h) { return h->use_single && h->cl_stride > 0 && !(h->model.has_rep && h->ap_run.S > 8); }
+bool split_supported(const ani_handle* h) { return h->use_single && h->cl_stride > 0 && (!h->model.has_rep || rep_folded(h)); }
 
 int check_args(ani_handle* h, int ntotal, int nlocal, long long npairs, int ago) {
   if (!h) return ANI_ERR_ARG;

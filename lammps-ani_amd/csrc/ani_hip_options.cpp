@@ -7,6 +7,7 @@ void ani_trace_pop(void) { roctxRangePop(); }
 void ani_trace_mark(const char* name) { if (name) roctxMarkA(name); }
 
 const char* ani_last_mlp_kernel(const ani_handle* h) { return h ? h->last_mlp_kernel : ""; }
+const char* ani_last_repulsion_kernel(const ani_handle* h) { return h ? h->last_rep_kernel : ""; }
 
 int ani_debug_get(ani_handle* h, ani_debug_view* out) {
   if (!h || !out) return ANI_ERR_ARG;

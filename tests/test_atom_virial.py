@@ -6,8 +6,8 @@ vatom order of the symmetric part.
 
 Reference: F^(i) of every centre from Oracle.aev_vjp with every dE/dAEV row zeroed except centre i's (the true rows from
 compute(want_aev=True)); for repulsion models (aev_vjp refuses them) the same network without the repulsion block (the synthetic
-generator appends it after the networks of the same seed) plus the half-pair term of every list entry, restated below from
-oracle/ani_oracle.c:rep_pair.  One small open fixture is cross-checked against central differences of the oracle's eatom.
+generator appends it after the networks of the same seed) plus the half-pair term of every list entry, restated in
+tests/repulsion_reference.py from oracle/ani_oracle.c:rep_pair.  One small open fixture is cross-checked against central differences of the oracle's eatom.
 
 Bars, derived from the bars the forces already meet (tests/test_hip_parity.py):
   fp32 handle   a row's component is a sum of at most n_j terms (x_j - x_i)_a F_b, |x_j - x_i| <= Rcr, each F off by at most
@@ -23,6 +23,7 @@ import pytest
 from conftest import GOLDEN_CASES, golden_input, golden_model_path, load_golden
 from lammps_ani_amd import harness as hx
 from lammps_ani_amd import model_file as mf
+from repulsion_reference import rep_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -52,29 +53,6 @@ def fold(W, inp):
     out = W[: inp.nlocal].copy()
     np.add.at(out, np.asarray(inp.owner_lidx, dtype=np.int64), W[inp.nlocal:])
     return out
-
-
-def rep_terms(inp, rep):
-    """half-pair repulsion of every full-list entry (i, j): d = x_j - x_i, g = dE/dx_j (Hartree/A); oracle/ani_oracle.c:rep_pair"""
-    i = np.repeat(np.asarray(inp.ilist, dtype=np.int64), inp.numneigh)
-    j = np.asarray(inp.jlist, dtype=np.int64)
-    d = inp.x[j] - inp.x[i]
-    r = np.sqrt((d * d).sum(1))
-    sa, sb = inp.species[i], inp.species[j]
-    cut = rep["cutoff"]
-    x = r / cut
-    den = 1.0 - x * x
-    ok = (r < cut) & (den > 1e-10)
-    den = np.where(ok, den, 1.0)
-    fc = np.exp(1.0 - 1.0 / den)
-    dfc = fc * (-(2.0 * x / cut) / (den * den))
-    a2b = 1.8897261258369282
-    db = r * a2b
-    y, al, k = rep["y_ab"][sa, sb], rep["sqrt_alpha_ab"][sa, sb], rep["k_rep_ab"][sa, sb]
-    g = y / db * np.exp(-al * db ** k)
-    dg = a2b * g * (-1.0 / db - al * k * db ** (k - 1.0))
-    de = np.where(ok, dg * fc + g * dfc, 0.0)
-    return i, j, d, (0.5 * de / np.where(r > 0, r, 1.0))[:, None] * d
 
 
 def reference(g, inp_full, model_cache, compat):
