@@ -83,12 +83,12 @@ int ani_md_check(double* d2max, const double* ev, double* out, void* stream);
  * Parameters: the defaults of LAMMPS `min_modify` are dtmax = 10 dt0, dtmin = 0.02 dt0, dtgrow 1.1, dtshrink 0.5, alpha0 0.25,
  * alphashrink 0.99, delaystep 20, initialdelay 1, halfstepback 1, dmax 0.1 A; dt0, etol, ftol and maxiter are the caller's.
  *
- * State: ANI_MD_FIRE_NSTATE doubles on the device, read by the host after a synchronisation:
- *   [0] iterations done   [1] dt   [2] alpha   [3] last_negative   [4] e_prev   [5] e_cur
- *   [6] P = sum v.f   [7] vv = sum v.v   [8] ff = sum f.f   (of the last iteration that was not frozen)
- *   [9] dtv of the last move   [10] uphill events   [11] dmax-limited moves
- *   [12] stop: 0 running, 1 etol, 2 ftol, 3 maxiter, 4 non-finite energy or force norm
- *   [13] energy and [14] ff of the start point (seen by iteration 1)   [15] largest |velocity component| of the last move
+ * State: ANI_MD_FIRE_NSTATE doubles on the device, read by the host after a synchronisation, indexed by the ANI_MD_FIRE_* enum below:
+ *   ITERATIONS done   DT   ALPHA   LAST_NEGATIVE   E_PREV   E_CUR
+ *   P = sum v.f   VV = sum v.v   FF = sum f.f   (of the last iteration that was not frozen)
+ *   DTV of the last move   UPHILL events   LIMITED: dmax-limited moves
+ *   STOP: 0 running, 1 etol, 2 ftol, 3 maxiter, 4 non-finite energy or force norm
+ *   E_FIRST and FF_FIRST: energy and ff of the start point (seen by iteration 1)   VMAX: largest |velocity component| of the last move
  *
  * ani_md_fire_init       fills the record (dt = dt0, alpha = alpha0, everything else 0) and zeroes v[nlocal][3].
  * ani_md_fire_work_size  doubles of scratch that ani_md_fire_iterate needs for nlocal atoms (no initialisation needed; the same
@@ -116,6 +116,11 @@ int ani_md_check(double* d2max, const double* ev, double* out, void* stream);
  *                        (out: 1 + ANI_MD_FIRE_NSTATE doubles).
  */
 #define ANI_MD_FIRE_NSTATE 16
+enum {
+  ANI_MD_FIRE_ITERATIONS = 0, ANI_MD_FIRE_DT, ANI_MD_FIRE_ALPHA, ANI_MD_FIRE_LAST_NEGATIVE, ANI_MD_FIRE_E_PREV, ANI_MD_FIRE_E_CUR,
+  ANI_MD_FIRE_P, ANI_MD_FIRE_VV, ANI_MD_FIRE_FF, ANI_MD_FIRE_DTV, ANI_MD_FIRE_UPHILL, ANI_MD_FIRE_LIMITED, ANI_MD_FIRE_STOP,
+  ANI_MD_FIRE_E_FIRST, ANI_MD_FIRE_FF_FIRST, ANI_MD_FIRE_VMAX
+};
 typedef struct ani_md_fire_params {
   double dt0, dtmax, dtmin, dtgrow, dtshrink, alpha0, alphashrink, dmax, etol, ftol;
   int delaystep, initialdelay, halfstepback, maxiter;
@@ -200,32 +205,43 @@ int ani_md_rattle_velocities(const double* x, double* v, const int* cl, const do
  *   The caller multiplies every velocity by s.  eta_dotdot is state: the first loop of a call uses the upper links' accelerations
  *   that the call before left.
  *
- * State: ANI_MD_NH_NSTATE doubles on the device:
- *   [0] half-steps done   [1] K2 after the scaling   [2] s of the last half-step   [3] its t_target   [4] ecouple   [5] tdof
- *   [6] calls that found K2 non-finite   [7] 0   [8..16) eta   [16..24) eta_dot   [24..32) eta_dotdot   (unused links stay 0)
- *   A call that finds K2 non-finite writes s = 1 (and [1] = that K2, [3], [5]), adds one to [6] and leaves [0], [4] and the chain.
+ * State: ANI_MD_NH_NSTATE doubles on the device, indexed by the ANI_MD_NH_* enum below:
+ *   HALF_STEPS done   K2 after the scaling   S of the last half-step   its T_TARGET   ECOUPLE   TDOF
+ *   NONFINITE: calls that found K2 non-finite   ZERO   ETA, ETA_DOT, ETA_DOTDOT: ANI_MD_NH_MAXCHAIN links each (unused links stay 0)
+ *   A call that finds K2 non-finite writes S = 1 (and K2 = that K2, T_TARGET, TDOF), adds one to NONFINITE and leaves HALF_STEPS,
+ *   ECOUPLE and the chain.
  *
  * ani_md_nh_work_size   doubles of scratch for nlocal atoms: one partial per block of 256 atoms (host function, no device).
  * ani_md_nh_init        zeroes the record.
  * ani_md_nh_kinetic     work[b] = K2 of the owned atoms of block b (b < ceil(nlocal / 256)); mass[nlocal] in g/mol.
- * ani_md_nh_chain       one workgroup.  npart > 0: K2 = work[0] + .. + work[npart - 1] in the fixed order;  npart == 0: K2 = state[1].
+ * ani_md_nh_chain       one workgroup.  npart > 0: K2 = work[0] + .. + work[npart - 1] in the fixed order;  npart == 0: K2 = state[ANI_MD_NH_K2].
  *                       Then the half-step above, and the whole record is written.  params is a host pointer.
- * ani_md_nh_scale       v *= state[2].
- * ani_md_nh_initial_integrate   v = state[2] v first, then ani_md_initial_integrate.
+ * ani_md_nh_scale       v *= state[ANI_MD_NH_S].
+ * ani_md_nh_initial_integrate   v = state[ANI_MD_NH_S] v first, then ani_md_initial_integrate.
  * ani_md_nh_final_integrate     ani_md_final_integrate without Langevin (f is not written), and in the same pass the partials of
  *                       ani_md_nh_kinetic on the new velocities into work: bit for bit what that call would write.
  *
  * ani_md_thermo: two launches (per-block partials of the six sums K_ab = sum_i m_i v_ia v_ib mvv2e in the order xx, yy, zz, xy, xz,
- * yz, then one workgroup) into out[ANI_MD_THERMO_N], with W_ab = ev[1 + 3 a + b] the pair virial and V = volume:
- *   [0] pe = ev[0]   [1] ke = (K_xx + K_yy + K_zz) / 2   [2] temp = 2 ke / (tdof k_B)
- *   [3] press = (K_xx + K_yy + K_zz + W_xx + W_yy + W_zz) / (3 V) nktv2p
- *   [4..10) P_ab = (K_ab + W_ab) / V nktv2p, xx yy zz xy xz yz   [10] etotal = pe + ke   [11] ecouple = nh_state[4] (0: NULL)
- *   [12] econserve = etotal + ecouple   [13] volume   [14] K2 = 2 ke   [15] 0
- *   with_virial == 0: [3..10) are NaN.  work: ani_md_thermo_work_size(nlocal) doubles.
+ * yz, then one workgroup) into out[ANI_MD_THERMO_N], indexed by the ANI_MD_THERMO_* enum below, with W_ab = ev[1 + 3 a + b] the pair
+ * virial and V = volume:
+ *   PE = ev[0]   KE = (K_xx + K_yy + K_zz) / 2   TEMP = 2 ke / (tdof k_B)
+ *   PRESS = (K_xx + K_yy + K_zz + W_xx + W_yy + W_zz) / (3 V) nktv2p
+ *   PXX PYY PZZ PXY PXZ PYZ: P_ab = (K_ab + W_ab) / V nktv2p   ETOTAL = pe + ke   ECOUPLE = nh_state[ANI_MD_NH_ECOUPLE] (0: NULL)
+ *   ECONSERVE = etotal + ecouple   VOL = volume   K2 = 2 ke   ZERO
+ *   with_virial == 0: PRESS .. PYZ are NaN.  work: ani_md_thermo_work_size(nlocal) doubles.
  */
 #define ANI_MD_NH_NSTATE 32
 #define ANI_MD_NH_MAXCHAIN 8
 #define ANI_MD_THERMO_N 16
+enum {
+  ANI_MD_NH_HALF_STEPS = 0, ANI_MD_NH_K2, ANI_MD_NH_S, ANI_MD_NH_T_TARGET, ANI_MD_NH_ECOUPLE, ANI_MD_NH_TDOF, ANI_MD_NH_NONFINITE,
+  ANI_MD_NH_ZERO, ANI_MD_NH_ETA = 8, ANI_MD_NH_ETA_DOT = 16, ANI_MD_NH_ETA_DOTDOT = 24
+};
+enum {
+  ANI_MD_THERMO_PE = 0, ANI_MD_THERMO_KE, ANI_MD_THERMO_TEMP, ANI_MD_THERMO_PRESS, ANI_MD_THERMO_PXX, ANI_MD_THERMO_PYY,
+  ANI_MD_THERMO_PZZ, ANI_MD_THERMO_PXY, ANI_MD_THERMO_PXZ, ANI_MD_THERMO_PYZ, ANI_MD_THERMO_ETOTAL, ANI_MD_THERMO_ECOUPLE,
+  ANI_MD_THERMO_ECONSERVE, ANI_MD_THERMO_VOL, ANI_MD_THERMO_K2, ANI_MD_THERMO_ZERO
+};
 typedef struct ani_md_nh_params {
   double dt, t_period, drag;
   int mtchain, nc_tchain;
@@ -272,21 +288,22 @@ int ani_md_thermo(const double* v, const double* mass, int nlocal, const double*
  *   5. barostat chain
  * This is FixNH's order for iso, mtk yes, pchain > 0.
  *
- * Conserved:  pe + ke + ecouple(thermostat, NH record [4]) + ecouple(barostat, record [21]) with
+ * Conserved:  pe + ke + ecouple(thermostat, ANI_MD_NH_ECOUPLE) + ecouple(barostat, ANI_MD_NPT_ECOUPLE) with
  *   ecouple(barostat) = 3 (W wd^2 / 2 + ecouple of the barostat chain) + p_target (V - V0) / nktv2p,   V0 the volume at ani_md_npt_init.
  * The factor 3: the three equal strain rates are one scalar here.
  *
- * Barostat record: ANI_MD_NPT_NSTATE doubles on the device:
- *   [0] half-steps done   [1] wd   [2] omega = sum dt wd   [3] P of the last strain-rate update   [4] its p_target   [5] W   [6] fv   [7] mu
- *   [8..11) box lo   [11..14) box len   [14..17) ratio of the last first half   [17..20) c   [20] V0   [21] ecouple(barostat)
- *   [22] half-steps that found K2, Wtr or the new wd non-finite   [23] N   [24..32) eta   [32..40) eta_dot   [40..48) eta_dotdot of the
- *   barostat chain (unused links stay 0)   [48] ecouple of the barostat chain alone   [49] V   [50..56) 0
- * A half-step that finds K2, Wtr or the new wd non-finite writes s = 1 into the NH record as ani_md_nh_chain does (with [1], [3], [5],
- * one more in [6]), fv = mu = 1 and ratio = 1 into this one, adds one to [22] and leaves [0], the box, wd and both chains.
+ * Barostat record: ANI_MD_NPT_NSTATE doubles on the device, indexed by the ANI_MD_NPT_* enum below:
+ *   HALF_STEPS done   OMEGA_DOT = wd   OMEGA = sum dt wd   PRESS: P of the last strain-rate update   its P_TARGET   W   FV   MU
+ *   LO, LEN: the box (three each)   RATIO of the last first half (three)   C (three)   V0   ECOUPLE(barostat)
+ *   NONFINITE: half-steps that found K2, Wtr or the new wd non-finite   NATOMS = N   ETA, ETA_DOT, ETA_DOTDOT of the barostat chain:
+ *   ANI_MD_NH_MAXCHAIN links each (unused links stay 0)   ECOUPLE_CHAIN: ecouple of the barostat chain alone   VOL = V   the rest 0
+ * A half-step that finds K2, Wtr or the new wd non-finite writes S = 1 into the NH record as ani_md_nh_chain does (with K2, T_TARGET,
+ * TDOF, one more in NONFINITE), fv = mu = 1 and ratio = 1 into this one, adds one to NONFINITE and leaves HALF_STEPS, the box, wd and
+ * both chains.
  *
  * ani_md_npt_init       fills the record: lo, len, c = lo + len / 2, V0 = V, N, fv = mu = ratio = 1, the rest 0 (host arguments).
  * ani_md_npt_chain      one workgroup.  phase 0: steps 1-4 and 6 of the first half; phase 1: steps 2-5 of the second.  npart > 0: K2 =
- *                       the partials in the fixed order of ani_md_nh_chain; npart == 0: K2 = nh_state[1].  Writes both records.
+ *                       the partials in the fixed order of ani_md_nh_chain; npart == 0: K2 = nh_state[ANI_MD_NH_K2].  Writes both records.
  *                       t_target and p_target (atm) are arguments: the host ramps them and reads nothing.  params: host pointer.
  * ani_md_npt_initial_integrate   step 5 on rows [0, nlocal) with the displacement fold of ani_md_initial_integrate against x_built
  *                       (which is NOT rescaled: the displacement includes the dilation), and step 7 on shift rows [0, nghost), in one
@@ -296,6 +313,12 @@ int ani_md_thermo(const double* v, const double* mass, int nlocal, const double*
  *                       (out: 1 + ANI_MD_NPT_NSTATE doubles).
  */
 #define ANI_MD_NPT_NSTATE 56
+enum {
+  ANI_MD_NPT_HALF_STEPS = 0, ANI_MD_NPT_OMEGA_DOT, ANI_MD_NPT_OMEGA, ANI_MD_NPT_PRESS, ANI_MD_NPT_P_TARGET, ANI_MD_NPT_W, ANI_MD_NPT_FV,
+  ANI_MD_NPT_MU, ANI_MD_NPT_LO = 8, ANI_MD_NPT_LEN = 11, ANI_MD_NPT_RATIO = 14, ANI_MD_NPT_C = 17, ANI_MD_NPT_V0 = 20, ANI_MD_NPT_ECOUPLE,
+  ANI_MD_NPT_NONFINITE, ANI_MD_NPT_NATOMS, ANI_MD_NPT_ETA = 24, ANI_MD_NPT_ETA_DOT = 32, ANI_MD_NPT_ETA_DOTDOT = 40,
+  ANI_MD_NPT_ECOUPLE_CHAIN = 48, ANI_MD_NPT_VOL
+};
 typedef struct ani_md_npt_params {
   double dt, t_period, drag, p_period;
   int mtchain, nc_tchain, mpchain, nc_pchain;
@@ -322,7 +345,7 @@ int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, d
  *   kappa[nr]      >= 0, kcal/mol/A^2 (distance) or kcal/mol/rad^2 (angle, torsion); PLUMED's KAPPA=100 kJ/mol/rad^2 is 23.9006
  *   centre[nr]     A or rad
  * Box: len = len3 (host pointer to three doubles) when box_dev == NULL, otherwise the three doubles at box_dev in device memory (the
- *   loop passes the barostat record's [11..14): the box of the moment).  Every difference vector is a minimum image,
+ *   loop passes the barostat record's ANI_MD_NPT_LEN words: the box of the moment).  Every difference vector is a minimum image,
  *   minimg(a)[k] = a[k] - len[k] rint(a[k] / len[k]) in the periodic dimensions (bit k of periodic_mask).
  * Bias:  e = kappa / 2 D^2,  F_i = -kappa D dcv/dx_i,  D = cv - centre; for a torsion D is folded into (-pi, pi]:
  *   D -= 2 pi rint(D / (2 pi)), then D += 2 pi where D <= -pi.
@@ -352,11 +375,11 @@ int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, d
  *   The same inputs give bitwise the same f, ev and record.
  *   A word of the table that points outside -- touched[t] outside [0, natoms), an entry outside [0, 4 nr) -- is skipped (an atom
  *   with all its entries, or the one entry), never followed, and the sums' workgroup counts such words: any of them makes E NaN
- *   (ev[0] and record [1]) like a non-finite restraint, so a table that drops force cannot pass for a good one.  row_ptr is
+ *   (ev[0] and the record's EBIAS) like a non-finite restraint, so a table that drops force cannot pass for a good one.  row_ptr is
  *   trusted: ascending, within entries.
- * Record: ANI_MD_RESTRAINT_NREC doubles on the device, zeroed by the caller at the start:
- *   [0] evaluations (one more per apply)   [1] E   [2..11) W   [11] non-finite restraints of this evaluation
- *   [12] the largest |D| among the finite ones   [13] skipped words of the gather table   [14..16) 0
+ * Record: ANI_MD_RESTRAINT_NREC doubles on the device, zeroed by the caller at the start, indexed by the ANI_MD_RESTRAINT_REC_* enum:
+ *   EVALUATIONS (one more per apply)   EBIAS = E   VIRIAL = W (nine)   NONFINITE restraints of this evaluation
+ *   MAX_DELTA: the largest |D| among the finite ones   SKIPPED words of the gather table   ZERO (two)
  * No alignment beyond that of the element types is asked of any pointer.
  * nr <= 0: both return 0 and launch nothing.
  */
@@ -364,6 +387,10 @@ int ani_md_npt_check(double* d2max, const double* ev, const double* npt_state, d
 #define ANI_MD_RESTRAINT_DISTANCE 0
 #define ANI_MD_RESTRAINT_ANGLE 1
 #define ANI_MD_RESTRAINT_TORSION 2
+enum {
+  ANI_MD_RESTRAINT_REC_EVALUATIONS = 0, ANI_MD_RESTRAINT_REC_EBIAS, ANI_MD_RESTRAINT_REC_VIRIAL, ANI_MD_RESTRAINT_REC_NONFINITE = 11,
+  ANI_MD_RESTRAINT_REC_MAX_DELTA, ANI_MD_RESTRAINT_REC_SKIPPED, ANI_MD_RESTRAINT_REC_ZERO
+};
 int ani_md_restraints_eval(const double* x, int natoms, const int* atoms, const int* kind, const double* kappa, const double* centre,
                            int nr, const double* len3, const double* box_dev, int periodic_mask, double* cv, double* e, double* fslot,
                            double* w, void* stream);

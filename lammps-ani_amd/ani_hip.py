@@ -56,9 +56,13 @@ class FireParams(C.Structure):
                                           "ftol")] + [(n, C.c_int) for n in ("delaystep", "initialdelay", "halfstepback", "maxiter")]
 
 
+# The device records of include/ani_md.h, one table per record: field -> its index, or the slice of a field of several words.  A field
+# is the header's enum member without its prefix (ANI_MD_NPT_OMEGA_DOT is NPT_LAYOUT["omega_dot"]; "P" and "W" are written as the
+# dicts below have always spelt them); tests/test_abi_exports.py holds the tables against the header.  "zero" words are padding.
 FIRE_NSTATE = 16
-FIRE_STATE_KEYS = ("iterations", "dt", "alpha", "last_negative", "e_prev", "e_cur", "P", "vv", "ff", "dtv", "uphill", "limited", "stop",
-                   "e_first", "ff_first", "vmax")
+FIRE_LAYOUT = dict(iterations=0, dt=1, alpha=2, last_negative=3, e_prev=4, e_cur=5, P=6, vv=7, ff=8, dtv=9, uphill=10, limited=11,
+                   stop=12, e_first=13, ff_first=14, vmax=15)
+FIRE_STATE_KEYS = tuple(FIRE_LAYOUT)
 FIRE_STOP_REASONS = ("running", "etol", "ftol", "maxiter", "non-finite")
 # ANI_MD_SHAKE_NSTATS words of include/ani_md.h (ani_md_shake_positions): the third is the bit pattern of a double
 SHAKE_NSTATS = 4
@@ -66,9 +70,12 @@ SHAKE_STATS_KEYS = ("unconverged", "max_iterations", "max_residual", "calls")
 # the Nose-Hoover chain's state record and the thermo record of include/ani_md.h (ani_md_nh_*, ani_md_thermo)
 NH_NSTATE = 32
 NH_MAXCHAIN = 8
-NH_STATE_KEYS = ("half_steps", "k2", "s", "t_target", "ecouple", "tdof", "nonfinite")
+NH_LAYOUT = dict(half_steps=0, k2=1, s=2, t_target=3, ecouple=4, tdof=5, nonfinite=6, zero=7, eta=slice(8, 16), eta_dot=slice(16, 24),
+                 eta_dotdot=slice(24, 32))
 THERMO_N = 16
-THERMO_KEYS = ("pe", "ke", "temp", "press", "pxx", "pyy", "pzz", "pxy", "pxz", "pyz", "etotal", "ecouple", "econserve", "vol", "k2")
+THERMO_LAYOUT = dict(pe=0, ke=1, temp=2, press=3, pxx=4, pyy=5, pzz=6, pxy=7, pxz=8, pyz=9, etotal=10, ecouple=11, econserve=12, vol=13,
+                     k2=14, zero=15)
+THERMO_KEYS = tuple(k for k in THERMO_LAYOUT if k != "zero")
 
 
 class NhParams(C.Structure):
@@ -76,18 +83,30 @@ class NhParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("t_period", C.c_double), ("drag", C.c_double), ("mtchain", C.c_int), ("nc_tchain", C.c_int)]
 
 
+def _record_dict(rec, layout, nlinks: int) -> dict:
+    """a record (host array) by its layout table: one-word fields as floats, longer ones as copies, of a chain's eta, eta_dot and
+    eta_dotdot the first nlinks links; padding left out"""
+    rec = np.asarray(rec, dtype=np.float64)
+    out = {}
+    for name, at in layout.items():
+        if name == "zero":
+            continue
+        if name.startswith("eta"):
+            at = slice(at.start, at.start + nlinks)
+        out[name] = rec[at].copy() if isinstance(at, slice) else float(rec[at])
+    return out
+
+
 def nh_state_dict(rec, mtchain: int = NH_MAXCHAIN) -> dict:
     """the ANI_MD_NH_NSTATE doubles of a chain record (host array) as a dict; eta, eta_dot, eta_dotdot: the first mtchain links"""
-    rec = np.asarray(rec, dtype=np.float64)
-    out = dict(zip(NH_STATE_KEYS, rec[:7].tolist()))
-    for k, name in enumerate(("eta", "eta_dot", "eta_dotdot")):
-        out[name] = rec[8 + 8 * k: 8 + 8 * k + mtchain].copy()
-    return out
+    return _record_dict(rec, NH_LAYOUT, mtchain)
 
 
 # the barostat record of include/ani_md.h (ani_md_npt_*)
 NPT_NSTATE = 56
-NPT_STATE_KEYS = ("half_steps", "omega_dot", "omega", "press", "p_target", "W", "fv", "mu")
+NPT_LAYOUT = dict(half_steps=0, omega_dot=1, omega=2, press=3, p_target=4, W=5, fv=6, mu=7, lo=slice(8, 11), len=slice(11, 14),
+                  ratio=slice(14, 17), c=slice(17, 20), v0=20, ecouple=21, nonfinite=22, natoms=23, eta=slice(24, 32),
+                  eta_dot=slice(32, 40), eta_dotdot=slice(40, 48), ecouple_chain=48, vol=49)
 
 
 class NptParams(C.Structure):
@@ -99,17 +118,12 @@ class NptParams(C.Structure):
 def npt_state_dict(rec, mpchain: int = NH_MAXCHAIN) -> dict:
     """the ANI_MD_NPT_NSTATE doubles of a barostat record (host array) as a dict; eta, eta_dot, eta_dotdot: the first mpchain links
     of the barostat chain"""
-    rec = np.asarray(rec, dtype=np.float64)
-    out = dict(zip(NPT_STATE_KEYS, rec[:8].tolist()))
-    out.update(lo=rec[8:11].copy(), len=rec[11:14].copy(), ratio=rec[14:17].copy(), c=rec[17:20].copy(), v0=float(rec[20]),
-               ecouple=float(rec[21]), nonfinite=float(rec[22]), natoms=float(rec[23]), ecouple_chain=float(rec[48]), vol=float(rec[49]))
-    for k, name in enumerate(("eta", "eta_dot", "eta_dotdot")):
-        out[name] = rec[24 + 8 * k: 24 + 8 * k + mpchain].copy()
-    return out
+    return _record_dict(rec, NPT_LAYOUT, mpchain)
 
 
 # the restraint record and the kinds of include/ani_md.h (ani_md_restraints_*): kind -> (code, atoms)
 RESTRAINT_NREC = 16
+RESTRAINT_LAYOUT = dict(evaluations=0, ebias=1, virial=slice(2, 11), nonfinite=11, max_delta=12, skipped=13, zero=slice(14, 16))
 RESTRAINT_KINDS = {"distance": (0, 2), "angle": (1, 3), "torsion": (2, 4)}
 
 
@@ -127,9 +141,11 @@ def restraint_gather_table(atoms):
 
 def restraint_state_dict(rec) -> dict:
     """the ANI_MD_RESTRAINT_NREC doubles of a restraint record (host array) as a dict"""
-    rec = np.asarray(rec, dtype=np.float64)
-    return dict(evaluations=int(rec[0]), ebias=float(rec[1]), virial=rec[2:11].reshape(3, 3).copy(), nonfinite=int(rec[11]),
-                max_delta=float(rec[12]), skipped=int(rec[13]))
+    out = _record_dict(rec, RESTRAINT_LAYOUT, 0)
+    out["virial"] = out["virial"].reshape(3, 3)
+    for name in ("evaluations", "nonfinite", "skipped"):
+        out[name] = int(out[name])
+    return out
 
 
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .ani_hip import NPT_LAYOUT, SHAKE_STATS_KEYS
+
 # LAMMPS `units real` constants (update.cpp of LAMMPS): forces kcal/mol/A, masses g/mol, time fs
 FTM2V = 1.0 / 48.88821291 / 48.88821291
 MVV2E = 48.88821291 * 48.88821291
@@ -97,13 +99,13 @@ def npt_rebuild_limit(skin, lo_built, len_built, lo_now, len_now, nimg_max) -> f
 
 class VerletRun:
     def __init__(self, ani, inp, box_len, device, dt: float = 0.5, cutoff: float = 5.1, skin: float = 2.0,
-                 ghost_margin: float = 0.0, every: int = 10, masses=ANI2X_MASSES, group=None, seed: int = 12345,
+                 every: int = 10, masses=ANI2X_MASSES, group=None, seed: int = 12345,
                  langevin=None, box_lo=None, grid=None, periodic=(True, True, True), overlap=None, native_comm=None,
                  force_collectives=False, vflag=False):
         """ani: ani_hip.ANI (full list, any precision); inp: harness.RankInput of this rank — only its OWNED atoms
         (positions, types, global tags) are taken, ghosts and lists are rebuilt here; langevin: None or
         (T_target, damp_fs) as ``fix langevin T T damp seed``; grid: processor grid (default comm.grid_for(world));
-        ghost_margin: ignored (kept for callers of the earlier fixed-ghost-shell version); overlap: run the two ghost
+        overlap: run the two ghost
         exchanges of a step on a second stream beside the rows that do not need them (the library's split step,
         include/ani_hip.h ani_step_*).  Cutting the step costs five more launches (+0.05 ms at 12 500 atoms per GPU,
         measured on one card), which the hidden exchanges have to pay back: default on with several ranks over RCCL (two
@@ -112,6 +114,10 @@ class VerletRun:
         (include/ani_comm.h) instead of torch.distributed collectives; force_collectives: a single rank takes the several-rank
         paths (one-participant collectives), so that one GPU can exercise them.  vflag: every force evaluation also
         accumulates the pair style's virial (``virial()``; LAMMPS sets vflag on thermo steps with a pressure compute)."""
+        if torch.device(device).type != "cuda":
+            raise ValueError(f"VerletRun needs a HIP device (torch device type 'cuda'), got {device!r}: every step of the loop is one of "
+                             "libani_hip's device entry points (include/ani_md.h, ani_build_list_device), which take device pointers")
+        from . import ani_hip
         from .comm import DomainComm, grid_for
         self.ani, self.device, self.group = ani, device, group
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -139,30 +145,25 @@ class VerletRun:
         self.since_build = 0
         self.nbuilds = 0
         self.npairs = 0
-        self._stream = torch.cuda.current_stream(device).cuda_stream if torch.device(device).type == "cuda" else None
-        # on the GPU the loop's own steps (fix nve, fix langevin, displacement check, one-rank ghost copies) are the fused
-        # kernels of include/ani_md.h; the tensor-operation forms below remain for reading and for other devices
-        self._fused = torch.device(device).type == "cuda"
+        self._stream = torch.cuda.current_stream(device).cuda_stream
         self._seed = int(seed)
-        if self._fused:
-            from . import ani_hip
-            self._md = ani_hip.lib()
-            self._d2max = torch.zeros(1, dtype=torch.float64, device=device)
-            self._sendbuf = torch.empty((0, 3), dtype=torch.float64, device=device)
-            self._recvbuf = torch.empty((0, 3), dtype=torch.float64, device=device)
-            ani.set_option("device_overwrite_forces", 1)   # no separate force_clear launch
+        # the loop's own steps (fix nve, fix langevin, displacement check, one-rank ghost copies) are the kernels of include/ani_md.h
+        self._md = ani_hip.lib()
+        self._d2max = torch.zeros(1, dtype=torch.float64, device=device)
+        self._sendbuf = torch.empty((0, 3), dtype=torch.float64, device=device)
+        self._recvbuf = torch.empty((0, 3), dtype=torch.float64, device=device)
+        ani.set_option("device_overwrite_forces", 1)   # no separate force_clear launch
         env = os.environ.get("ANI_MD_OVERLAP")
         # default off: cutting the step costs +0.05 ms on one card and its benefit has not been measured on several
         want = False if overlap is None else bool(overlap)
         if env is not None and overlap is None:
             want = env not in ("", "0")
-        self._overlap = bool(want and self._fused)
+        self._overlap = bool(want)
         self._want_fold = os.environ.get("ANI_MD_FOLD", "1") not in ("", "0")   # measurement knob: 0 keeps the two ghost kernels
         self._fold = False
-        # one rank on the GPU: re-neighbouring (position wrap, ghost shell, buffers, displacement check) through the kernels of
+        # one rank: re-neighbouring (position wrap, ghost shell, buffers, displacement check) through the kernels of
         # include/ani_md.h instead of tensor operations; ANI_MD_NATIVE_REBUILD=0 keeps the tensor forms (measurements, tests)
-        self._native_rebuild = bool(self._fused and not self.dc.multi and
-                                    os.environ.get("ANI_MD_NATIVE_REBUILD", "1") not in ("", "0"))
+        self._native_rebuild = bool(not self.dc.multi and os.environ.get("ANI_MD_NATIVE_REBUILD", "1") not in ("", "0"))
         self._cap = 0
         self._cons = None      # bond constraints (set_constraints): None, or the device tables and parameters of the two stages
         self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
@@ -201,26 +202,19 @@ class VerletRun:
 
     def _per_atom_factors(self):
         """mass-dependent factors of the integrator, expanded once per re-neighbouring (atoms may have migrated) so
-        that each update is ONE fused device kernel"""
+        that each update is ONE device kernel"""
         n = self.nlocal
         if not self.dc.multi and getattr(self, "_factors_n", -1) == n:
             return   # one rank: nobody migrates, the owned atoms keep their order
         self._factors_n = n
         m = self.masses[self.species[:n].long()]
         self.mass = m[:, None]
-        self._dtfm1 = (0.5 * self.dt * FTM2V) / m                        # [n], the fused kernels' form
-        self._lang = None
+        self._dtfm1 = (0.5 * self.dt * FTM2V) / m                        # [n], the kernels' form
         self._g1 = self._g2 = None
         if self.langevin is not None:
             T, damp = self.langevin
             self._g1 = m * (-1.0 / damp / FTM2V)
             self._g2 = torch.sqrt(m) * ((24.0 * BOLTZ * T / damp / self.dt / MVV2E) ** 0.5 / FTM2V)
-        if self._fused:
-            return   # the [n, 3] forms below are the operands of the tensor-operation steps only
-        self._dtf_over_m = self._dtfm1[:, None].expand(-1, 3).contiguous()
-        if self.langevin is not None:
-            self._lang = (self._g1[:, None].expand(-1, 3).contiguous(), self._g2[:, None].expand(-1, 3).contiguous(),
-                          torch.empty((n, 3), dtype=torch.float64, device=self.device))
 
     def _grow(self, ntotal: int):
         """capacity buffers of the per-atom arrays that include ghosts (grown 1.5x, owned rows kept)"""
@@ -342,12 +336,11 @@ class VerletRun:
         # one rank: every ghost is an image of an owned atom -- the library's first and last kernel of a step do the two ghost
         # exchanges themselves (ani_set_ghost_fold); the maps belong to this list
         self._fold = False
-        if self._fused and self._want_fold and not self.dc.multi and self.ani.use_single and not self._overlap:
+        if self._want_fold and not self.dc.multi and self.ani.use_single and not self._overlap:
             self.ani.set_ghost_fold(self.dc.send_idx.data_ptr(), self.dc.send_shift.data_ptr(), self.ntotal - n, stream=self._stream)
             self._fold = True
         self.x_built = self.x[:n].clone()
-        if self._fused:
-            self._d2max.zero_()
+        self._d2max.zero_()
         self.since_build = 0
         self.nbuilds += 1
 
@@ -356,9 +349,7 @@ class VerletRun:
             raise RuntimeError(f"ani_md kernel launch failed (hipError {rc})")
 
     def _forces(self):
-        """force_clear + PairANI::compute + reverse communication of the ghost forces"""
-        if not self._fused:
-            self.f.zero_()
+        """PairANI::compute (which overwrites f: no force_clear) + reverse communication of the ghost forces"""
         self.ani.compute_device(self.ntotal, self.nlocal, None, self.x.data_ptr(), self.npairs, None, None, None, 1,
                                 self.f.data_ptr(), self.ev.data_ptr(), vflag=self.vflag, stream=self._stream)
         if not self._fold:   # folded: the finish kernel has added the images' rows into their owners'
@@ -366,13 +357,10 @@ class VerletRun:
 
     def _post_force(self):
         """fix langevin (LAMMPS fix_langevin.cpp, uniform random numbers in [-0.5, 0.5)): f += g1 v + g2 r on owned atoms.
-        Tensor-operation form: set-up, and devices without the fused kernels (step() fuses it with final_integrate)."""
+        Tensor-operation form from the [n] factors: it runs once, at set-up (a step has it inside ani_md_final_integrate)."""
         if self._g1 is not None:
-            if self._lang is not None:
-                g1, g2, r = self._lang
-            else:   # fused mode keeps only the [n] factors: this form runs once, at set-up
-                g1, g2 = self._g1[:, None], self._g2[:, None]
-                r = torch.empty((self.nlocal, 3), dtype=torch.float64, device=self.device)
+            g1, g2 = self._g1[:, None], self._g2[:, None]
+            r = torch.empty((self.nlocal, 3), dtype=torch.float64, device=self.device)
             r.uniform_(-0.5, 0.5, generator=self.gen)
             fl = self.f[: self.nlocal]
             fl.addcmul_(g1, self.v)
@@ -403,7 +391,7 @@ class VerletRun:
 
     # ---- the schedule of a step: first half, middle, second half ---------------------------------------
     def _first_half(self, t_target=None, npart: int = 0, p_target=None):
-        """fix nve / fix nvt initial_integrate: v += dtf f / m ; x += dt v  (fused: + the displacement maximum of check_distance),
+        """fix nve / fix nvt initial_integrate: v += dtf f / m ; x += dt v  (+ the displacement maximum of check_distance),
         behind the chain's half-step with a thermostat (v = s v first); with a barostat the chains' half-step that also moves the box
         in its record, then the dilated move of the atoms and the scaling of the ghost shifts in one launch; then the position
         stage of the constraints"""
@@ -421,13 +409,10 @@ class VerletRun:
             self._check(self._md.ani_md_nh_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
                                                              self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
                                                              self._d2max.data_ptr(), nvt["state"].data_ptr(), self._stream))
-        elif self._fused:
+        else:
             self._check(self._md.ani_md_initial_integrate(self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(),
                                                           self._dtfm1.data_ptr(), self.dt, self.nlocal, self.x_built.data_ptr(),
                                                           self._d2max.data_ptr(), self._stream))
-        else:
-            self.v.addcmul_(self.f[: self.nlocal], self._dtf_over_m)
-            self.x[: self.nlocal].add_(self.v, alpha=self.dt)
         if self._cons is not None:
             self._shake_positions()
 
@@ -478,10 +463,10 @@ class VerletRun:
                p_from=None, p_to=None):
         """nsteps steps of first half, middle, second half; with a thermostat the target goes from t_from (exclusive) to t_to (at
         the last step), and the call begins with the sum of the velocities as they are.  The one exception to the three pieces:
-        where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints,
-        the device loop -- the two are ONE launch, which carries the number of the step that ends."""
+        where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints --
+        the two are ONE launch, which carries the number of the step that ends."""
         nvt = self._nvt
-        one_launch = self._fused and nvt is None and self._cons is None
+        one_launch = nvt is None and self._cons is None
         t = p = None
         if nvt is not None:
             self._nvt_kinetic()
@@ -523,10 +508,6 @@ class VerletRun:
         the nsteps."""
         if nsteps <= 0:
             return
-        if not self._fused:
-            for _ in range(nsteps):
-                self.step()
-            return
         nvt, npt = self._nvt, self._npt
         if nvt is None:
             self._steps(int(nsteps), None, None, False, before_forces, after_forces)
@@ -543,7 +524,7 @@ class VerletRun:
         not finite -- the device entry point cannot return ANI_ERR_CAPACITY (nothing synchronises), it turns the energy into NaN
         instead, and this host round trip carries that along -- and, with constraints, when a cluster solve did not converge (the
         stats words sit behind the maximum: the same read).  With native re-neighbouring one kernel and one pinned read;
-        otherwise the tensor form and an all-reduce over the ranks.  extra: (state, device words, pinned words) of minimize(),
+        otherwise a copy of the word and an all-reduce over the ranks.  extra: (state, device words, pinned words) of minimize(),
         whose check kernel puts the FIRE record behind the maximum; minimize() judges the two together, with on_look in between.
         word: a scratch word in place of the loop's own maximum (warm_paths: nothing is zeroed that the loop needs, nothing is
         judged)."""
@@ -563,12 +544,8 @@ class VerletRun:
             torch.cuda.current_stream(self.device).synchronize()
             worst = float(host[0])    # the running maximum, or +inf when the last energy is not finite
         else:
-            if self._fused:
-                d2 = d2max.clone()    # running maximum since the last look (monotone between rebuilds: same decision)
-                d2max.zero_()
-            else:
-                d2 = (self.x[: self.nlocal] - self.x_built).square().sum(1).max().reshape(1) if self.nlocal else \
-                    torch.zeros(1, dtype=torch.float64, device=self.device)
+            d2 = d2max.clone()    # running maximum since the last look (monotone between rebuilds: same decision)
+            d2max.zero_()
             d2 = torch.where(torch.isfinite(self.ev[:1]), d2, torch.full_like(d2, float("inf")))
             worst = self._allreduce_max(d2.clone())
         if extra is not None or word is not None:
@@ -578,7 +555,7 @@ class VerletRun:
                                "capacity (ANI_ERR_CAPACITY) or the forces diverged")
         if npt is not None:
             rec = npt["chk_host"][1:].numpy()
-            self._set_box(rec[8:11], rec[11:14])
+            self._set_box(rec[NPT_LAYOUT["lo"]], rec[NPT_LAYOUT["len"]])
             npt["fresh"] = True
         if self._cons is not None and self._native_rebuild:
             self._constraint_health(self._chk_host[1:])
@@ -597,9 +574,7 @@ class VerletRun:
         """forward exchange: x[nlocal:] <- the owners' positions (+ image shifts); kernels and native messages on `stream`, the
         all-to-all on torch's current stream"""
         dc = self.dc
-        if not self._fused:
-            dc.forward_positions(self.x)
-        elif not dc.multi:
+        if not dc.multi:
             self._check(self._md.ani_md_forward_ghosts(self.x.data_ptr(), dc.send_idx.data_ptr(), dc.send_shift.data_ptr(),
                                                        self.nlocal, self.ntotal - self.nlocal, stream))
         elif self.native is not None:
@@ -637,9 +612,7 @@ class VerletRun:
 
     def _reverse_ghosts(self):
         """reverse exchange of the ghost forces on the loop's stream, both halves back to back"""
-        if not self._fused:
-            self.dc.reverse_add(self.f)
-        elif self.dc.multi and self.native is not None:
+        if self.dc.multi and self.native is not None:
             self.native.reverse(self.f.data_ptr(), self.nlocal, stream=self._stream)   # both halves; one kernel with one participant
         else:
             self._reverse_send(self._stream)
@@ -754,8 +727,6 @@ class VerletRun:
             raise RuntimeError("VerletRun.set_nvt: the run has a Langevin thermostat (langevin=...); one temperature control at a time")
         if self.dc.multi:
             raise RuntimeError("VerletRun.set_nvt: one rank only (the kinetic energy is not reduced over ranks)")
-        if not self._fused:
-            raise RuntimeError("VerletRun.set_nvt needs the device loop (the chain's kernels have no tensor-operation form)")
         t_start = float(t_start)
         t_stop = t_start if t_stop is None else float(t_stop)
         t_period = 100.0 * self.dt if t_period is None else float(t_period)
@@ -871,7 +842,7 @@ class VerletRun:
     def _npt_read_box(self):
         """one synchronising read of the barostat record; the host's copy of the box follows it.  Returns the record."""
         rec = self._npt["state"].cpu().numpy()
-        self._set_box(rec[8:11], rec[11:14])
+        self._set_box(rec[NPT_LAYOUT["lo"]], rec[NPT_LAYOUT["len"]])
         self._npt["fresh"] = True
         return rec
 
@@ -971,8 +942,9 @@ class VerletRun:
     @staticmethod
     def _stats_record(words) -> dict:
         """the ANI_MD_SHAKE_NSTATS words (a float64 tensor on the host that carries their bit patterns) as a dict"""
-        u = words.numpy().view(np.uint64)
-        return dict(unconverged=int(u[0]), max_iterations=int(u[1]), max_residual=float(u[2:3].view(np.float64)[0]), calls=int(u[3]))
+        rec = {k: int(w) for k, w in zip(SHAKE_STATS_KEYS, words.numpy().view(np.uint64))}
+        rec["max_residual"] = float(np.array(rec["max_residual"], dtype=np.uint64).view(np.float64))
+        return rec
 
     def _constraint_health(self, words):
         rec = self._stats_record(words)
@@ -1091,7 +1063,7 @@ class VerletRun:
     def _restraint_forces(self, sample: bool):
         """the two launches behind a force evaluation; the box of the moment comes from the barostat's record when there is one"""
         rs, md, st, n = self._restr, self._md, self._stream, self.nlocal
-        box_dev = self._npt["state"][11:14].data_ptr() if self._npt is not None else None
+        box_dev = self._npt["state"][NPT_LAYOUT["len"]].data_ptr() if self._npt is not None else None
         self._check(md.ani_md_restraints_eval(self.x.data_ptr(), n, rs["atoms"].data_ptr(), rs["kind"].data_ptr(), rs["kappa"].data_ptr(),
                                               rs["centre"].data_ptr(), rs["nr"], self._len3.ctypes.data, box_dev, self._pmask,
                                               rs["cv"].data_ptr(), rs["e"].data_ptr(), rs["fslot"].data_ptr(), rs["w"].data_ptr(), st))
@@ -1158,15 +1130,11 @@ class VerletRun:
 
     def _final_integrate(self):
         # fix langevin post_force + fix nve final_integrate
-        if self._fused:
-            lang = self._g1 is not None
-            self._check(self._md.ani_md_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.nlocal,
-                                                        1 if lang else 0, self._g1.data_ptr() if lang else None,
-                                                        self._g2.data_ptr() if lang else None, self.tag.data_ptr(), self._seed,
-                                                        self.step_no, self._stream))
-        else:
-            self._post_force()
-            self.v.addcmul_(self.f[: self.nlocal], self._dtf_over_m)
+        lang = self._g1 is not None
+        self._check(self._md.ani_md_final_integrate(self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.nlocal,
+                                                    1 if lang else 0, self._g1.data_ptr() if lang else None,
+                                                    self._g2.data_ptr() if lang else None, self.tag.data_ptr(), self._seed,
+                                                    self.step_no, self._stream))
 
     def warm_paths(self):
         """Run once, without touching the trajectory, the pieces of the loop that only some steps execute — the displacement
@@ -1268,8 +1236,8 @@ class VerletRun:
         without ``vflag``, and while constraints are set (the constraint virial is not accumulated).  With restraints set
         (set_restraints) pe, etotal and econserve include the bias energy and the pressure entries the bias virial.  One rank on
         the device.  The first call also sums the masses for the density, once."""
-        if self.dc.multi or not self._fused:
-            raise RuntimeError("VerletRun.thermo: one rank on the device only (the sums are not reduced over ranks)")
+        if self.dc.multi:
+            raise RuntimeError("VerletRun.thermo: one rank only (the sums are not reduced over ranks)")
         from . import ani_hip
         n = self.nlocal
         if self._thermo_buf is None or self._thermo_buf["n"] != n:
@@ -1279,7 +1247,7 @@ class VerletRun:
                                     out=torch.zeros(ani_hip.THERMO_N, dtype=torch.float64, device=self.device))
         b = self._thermo_buf
         npt_rec = self._npt_read_box() if self._npt is not None else None
-        vol = float(np.prod(self._box_len_np)) if npt_rec is None else float(npt_rec[49])
+        vol = float(np.prod(self._box_len_np)) if npt_rec is None else float(npt_rec[NPT_LAYOUT["vol"]])
         self._check(self._md.ani_md_thermo(self.v.data_ptr(), b["mass"].data_ptr(), n, self.ev.data_ptr(),
                                            1 if (self.vflag and self._cons is None) else 0, 3.0 * n - 3.0 - self._ncons, vol,
                                            self._nvt["state"].data_ptr() if self._nvt is not None else None, b["work"].data_ptr(),
@@ -1287,7 +1255,7 @@ class VerletRun:
         rec = dict(zip(ani_hip.THERMO_KEYS, b["out"].cpu().tolist()))
         del rec["k2"]
         if npt_rec is not None:       # the barostat's part: chain, strain rate and p_target (V - V0)
-            rec["ecouple"] += float(npt_rec[21])
+            rec["ecouple"] += float(npt_rec[NPT_LAYOUT["ecouple"]])
             rec["econserve"] = rec["etotal"] + rec["ecouple"]
         rec["density"] = b["mtot"] / vol / 0.602214129      # g/mol/A^3 -> g/cm^3 (LAMMPS units real, mv2d)
         return rec

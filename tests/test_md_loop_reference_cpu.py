@@ -80,9 +80,19 @@ def _langevin_factors(masses_of_atoms, T, damp, dt):
     from lammps_ani_amd import md
     species = torch.arange(len(masses_of_atoms), dtype=torch.int32)
     run = SimpleNamespace(nlocal=len(masses_of_atoms), dc=SimpleNamespace(multi=False), species=species,
-                          masses=torch.as_tensor(np.asarray(masses_of_atoms, dtype=np.float64)), dt=dt, langevin=(T, damp), _fused=True)
+                          masses=torch.as_tensor(np.asarray(masses_of_atoms, dtype=np.float64)), dt=dt, langevin=(T, damp))
     md.VerletRun._per_atom_factors(run)
     return run._dtfm1.numpy(), run._g1.numpy(), run._g2.numpy()
+
+
+def test_verlet_run_refuses_a_device_without_the_library_entry_points():
+    """every step of the loop is a device entry point of libani_hip: a CPU device is refused before anything else is touched"""
+    import torch
+    from lammps_ani_amd import md
+    with pytest.raises(ValueError, match="device entry points"):
+        md.VerletRun(None, None, np.ones(3), device=torch.device("cpu"))
+    with pytest.raises(ValueError, match="device entry points"):
+        md.VerletRun(None, None, None, "cpu")
 
 
 def free_particle_masses(n):

@@ -21,7 +21,7 @@ if os.environ.get("MLP_ARITH"):   # 2 (default): two-term fp16 splits, 1: exact 
     ani.set_option("mlp_arith", int(os.environ["MLP_ARITH"]))
     print("mlp_arith", os.environ["MLP_ARITH"])
 dev = torch.device("cuda:0")
-run = md.VerletRun(ani, inp, sysm.boxhi - sysm.boxlo, dev, dt=dt, ghost_margin=margin, box_lo=sysm.boxlo, langevin=lang)
+run = md.VerletRun(ani, inp, sysm.boxhi - sysm.boxlo, dev, dt=dt, box_lo=sysm.boxlo, langevin=lang)
 # list check against the harness at set-up
 inp7 = harness.decompose(sysm, skin=2.0 + margin)  # ghosts identical; host list has the wider cutoff, so rebuild at 7.1
 nn, jl = ani.debug_list(inp.nlocal)
