@@ -1,7 +1,8 @@
 """Inputs, references and bars of the AEV-stage edge tests (tests/test_aev_edges_cpu.py, tests/test_aev_edges.py).  No GPU.
 
-What picks an AEV kernel (``launch_nbr_compact``, ``launch_aev_forward``, ``launch_aev_forward_fused``, ``launch_aev_backward``
-in ani_kernels_aev.hip): the model shape (8x4, 4x8, generic), ``compat``, the longest candidate list (<= 128, <= 192, <= 256, more),
+What picks an AEV kernel (``fast_plan()`` in ani_aev_launch.h, read by ``launch_nbr_compact`` in ani_kernels_aev_lists.hip and by
+``launch_aev_forward``, ``launch_aev_forward_fused``, ``launch_aev_backward`` in ani_kernels_aev_fast.hip): the model shape (8x4, 4x8,
+generic), ``compat``, the longest candidate list (<= 128, <= 192, <= 256, more),
 the width of the pruned AEV row (<= 256 floats or more) and the virial flag; the per-centre lists sit in LDS behind two
 capacities, ``kMaxAng`` = 96 and ``radial_cap()`` = 3/4 of the longest list, at least 128, in steps of 64 (the whole list in
 compat mode).  The cases here are each the smallest input that reaches one of those edges.
@@ -48,7 +49,7 @@ RCR_ANI2X = 5.1
 
 
 def radial_cap(max_numneigh, compat):
-    """ani_kernels_aev.hip, radial_cap(): slots of the per-centre radial list"""
+    """ani_aev_launch.h, radial_cap(): slots of the per-centre radial list"""
     full = max(64, -(-max_numneigh // 64) * 64)
     if compat:
         return full

@@ -36,6 +36,23 @@ def test_every_header_under_include_is_exported():
     assert seen >= 28
 
 
+def test_makefile_objects_are_the_sources_of_csrc():
+    """The library is linked from OBJS of csrc/Makefile: one object per *.hip and *.cpp of csrc, no other.  A unit left out of the
+    list would show only as an unresolved symbol when the library is loaded.  The LAMMPS adapter (pair_ani.cpp, ani_plugin.cpp) is
+    not part of the library: it is built against LAMMPS' headers into the plugin."""
+    csrc = os.path.join(ROOT, "lammps-ani_amd", "csrc")
+    adapter = {"pair_ani.cpp", "ani_plugin.cpp"}
+    sources = sorted(n for n in os.listdir(csrc) if n.endswith((".hip", ".cpp")) and n not in adapter)
+    assert len(sources) >= 20 and adapter <= set(os.listdir(csrc))
+    text = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    lists = re.findall(r"^OBJS\s*\+?=(.*)$", text, flags=re.M)
+    assert lists
+    objs = " ".join(lists).split()
+    assert len(objs) == len(set(objs)), sorted(o for o in set(objs) if objs.count(o) > 1)
+    assert sorted(objs) == sorted(os.path.splitext(n)[0] + ".o" for n in sources)
+    assert len({os.path.splitext(n)[0] for n in sources}) == len(sources)   # no x.hip beside x.cpp: they would share an object
+
+
 def test_create_fails_loudly_without_gpu_or_for_cpu_device(tmp_path):
     """No GPU in the build container: ani_create must return an error, never fall back."""
     import torch

@@ -1,5 +1,7 @@
 """per-phase cycle counts of the AEV backward kernel (a -DABLB_STAMPS build: tools/abl_build.sh aev STAMPS "-DABLB_STAMPS"):
-ANI_HIP_LIB=tools/abl/libani_STAMPS.so python tools/bwd_stamps.py [atoms]"""
+ANI_HIP_LIB=tools/abl/libani_STAMPS.so python tools/bwd_stamps.py [atoms]
+The forward phases are those of aev_forward_fast: with the default options the forward pass is aev_forward_fused, which keeps no
+stamps, and the forward lines read 0; ANI_AEV_FUSED=0 in the environment takes the two-kernel route."""
 import ctypes as C
 import os
 import sys

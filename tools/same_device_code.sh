@@ -18,7 +18,7 @@ if [ $per_kernel = 1 ]; then
   new_files=("$@")
   if [ ${#old_files[@]} = 0 ] || [ ${#new_files[@]} = 0 ]; then echo "usage: $0 --per-kernel REV old.hip [...] -- new.hip [...]" >&2; exit 2; fi
 else
-  files=${*:-ani_kernels_aev.hip ani_kernels_mlp.hip ani_kernels_mlpf.hip ani_kernels_mlpg.hip}
+  files=${*:-ani_kernels_aev_lists.hip ani_kernels_aev_fast.hip ani_kernels_aev_generic.hip ani_kernels_mlp.hip ani_kernels_mlpf.hip ani_kernels_mlpg.hip}
   old_files=($files); new_files=($files)
 fi
 flags=$(make -s -C "$root/lammps-ani_amd/csrc" --eval='print-cxxflags: ; @echo $(CXXFLAGS)' print-cxxflags)
