@@ -148,6 +148,40 @@ def restraint_state_dict(rec) -> dict:
     return out
 
 
+# include/ani_md_transport.h: the outputs of ani_md_msd_sample per group (the header's ANI_MD_MSD_* enum), and its limits
+MSD_MAXCLASS = 16
+MSD_MAXGROUP = 8
+MSD_NOUT = 12
+MSD_LAYOUT = dict(msd=slice(0, 4), com=slice(4, 8), dcm=slice(8, 11), nonfinite=11)
+
+
+def msd_classes(membership):
+    """The classes of ani_md_msd_sample from membership [ngroup, n] (bool: atom i belongs to group g): the distinct membership
+    patterns, numbered in the order of their first atom.  Returns (cls [n] int32, -1 for an atom in no group; group_mask [ngroup]
+    int32, bit c set when class c belongs to the group; nclass)."""
+    member = np.asarray(membership, dtype=bool)
+    ngroup, n = member.shape
+    pattern = (member.astype(np.int64) << np.arange(ngroup, dtype=np.int64)[:, None]).sum(0)
+    cls = np.full(n, -1, dtype=np.int32)
+    masks = np.zeros(ngroup, dtype=np.int64)
+    seen = {}
+    for i in np.flatnonzero(pattern).tolist():
+        c = seen.setdefault(int(pattern[i]), len(seen))
+        cls[i] = c
+    for pat, c in seen.items():
+        for g in range(ngroup):
+            if (pat >> g) & 1:
+                masks[g] |= 1 << c
+    return cls, masks.astype(np.int32), len(seen)
+
+
+def msd_dict(row, count: int) -> dict:
+    """the ANI_MD_MSD_NOUT doubles of one group (host array) as a dict: msd [4], msd_com [4], dcm [3], count, nonfinite"""
+    row = np.asarray(row, dtype=np.float64)
+    return dict(msd=row[MSD_LAYOUT["msd"]].copy(), msd_com=row[MSD_LAYOUT["com"]].copy(), dcm=row[MSD_LAYOUT["dcm"]].copy(),
+                count=int(count), nonfinite=int(row[MSD_LAYOUT["nonfinite"]]))
+
+
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
     """ani_md_fire_params with the defaults of LAMMPS `min_modify` (dtmax = 10 dt0, dtmin = 0.02 dt0, ...); kw overrides them"""
     vals = dict(dt0=float(dt0), dtmax=10.0 * dt0, dtmin=0.02 * dt0, dtgrow=1.1, dtshrink=0.5, alpha0=0.25, alphashrink=0.99,
@@ -292,6 +326,15 @@ def lib():
         L.ani_md_restraints_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        # include/ani_md_transport.h: image flags, unwrapped positions, mean-squared displacements, trajectory frames
+        L.ani_md_wrap_positions_images.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ani_md_unwrap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ani_md_msd_work_size.argtypes = [C.c_int, C.c_int]
+        L.ani_md_msd_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_double, C.c_void_p, C.c_void_p]
+        L.ani_md_frame_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

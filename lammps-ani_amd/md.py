@@ -171,6 +171,10 @@ class VerletRun:
         self._nvt = None       # Nose-Hoover chain (set_nvt): None, or the device record, scratch and parameters
         self._npt = None       # isotropic barostat (set_npt): None, or the device record, its check buffers, parameters and targets
         self._restr = None     # umbrella restraints (set_restraints): None, or the device tables, outputs, record and series
+        self._img = None       # image flags (set_images): None, or the [nlocal, 3] int32 table that the wrap keeps
+        self._msd = None       # mean-squared displacements (set_msd): None, or the classes, the origin, scratch, outputs and series
+        self._dump = None      # trajectory frames (set_dump): None, or the device ring, its host side and the DCD writer
+        self._tag_order = None  # the owned atoms in ascending order of their global tag (_tag_rank), made at first use
         self._thermo_buf = None
         if self._overlap:
             # ANI_MD_OVERLAP_ONE_STREAM: measurement knob, the same cut step with everything on the compute stream
@@ -249,7 +253,11 @@ class VerletRun:
         if self._npt is not None and not self._npt["fresh"]:
             self._npt_read_box()      # a rebuild that no look of the host precedes: one read of the record
         x = self._xbuf
-        self._check(md.ani_md_wrap_positions(x.data_ptr(), n, self._lo3.ctypes.data, self._len3.ctypes.data, self._pmask, st))
+        if self._img is None:
+            self._check(md.ani_md_wrap_positions(x.data_ptr(), n, self._lo3.ctypes.data, self._len3.ctypes.data, self._pmask, st))
+        else:     # the same wrap, which adds the box lengths it removes to the image flags
+            self._check(md.ani_md_wrap_positions_images(x.data_ptr(), self._img.data_ptr(), n, self._lo3.ctypes.data,
+                                                        self._len3.ctypes.data, self._pmask, st))
         ng = 0
         nblk = max((n + 255) // 256, 1)
         half = max(self._ncombo, 1) * nblk
@@ -426,6 +434,13 @@ class VerletRun:
         # on every path above the ghost rows of x are now the images of this step's owned positions
         if self._rdf_every and self.step_no % self._rdf_every == 0:
             self.ani.rdf_accumulate_device(self.ntotal, self.nlocal, self.x.data_ptr(), stream=self._stream)
+        msd, dump = self._msd, self._dump
+        if msd is not None and msd["stride"] and self.step_no % msd["stride"] == 0:
+            row = msd["series"][msd["nsamples"] % msd["capacity"]].data_ptr()
+            msd["nsamples"] += 1
+            self._msd_sample(row)
+        if dump is not None and self.step_no % dump["every"] == 0:
+            self._dump_frame()
 
     def _rebuild_limit(self) -> float:
         """what the worst squared displacement of a look is held against: (skin / 2)^2, or npt_rebuild_limit with the box of the
@@ -1104,6 +1119,258 @@ class VerletRun:
         if reset:
             rs["nsamples"] = 0
         return dict(step=rows[:, 0].astype(np.int64), cv=rows[:, 1:1 + nr].copy(), ebias=rows[:, 1 + nr:].copy(), dropped=max(0, ns - cap))
+
+    # ---- image flags, mean-squared displacements, trajectory frames ---------------------------------------------
+    def _transport_guard(self, who: str):
+        if self.dc.multi:
+            raise RuntimeError(f"VerletRun.{who}: one rank only (the image flags would have to migrate with their atoms)")
+        if not self._native_rebuild:
+            raise RuntimeError(f"VerletRun.{who} needs the device loop with native re-neighbouring (one rank on the GPU)")
+
+    def _tag_rank(self):
+        """(order [n]: the local index of the atom with the k-th smallest global tag; rank [n] int32 on the device: its inverse, where
+        atom i goes in a table by tag).  One rank with native re-neighbouring: the owned atoms keep their order, made once."""
+        if self._tag_order is None:
+            order = np.argsort(self.tag.cpu().numpy(), kind="stable")
+            rank = np.empty(self.nlocal, dtype=np.int32)
+            rank[order] = np.arange(self.nlocal, dtype=np.int32)
+            self._tag_order, self._tag_rank_dev = order, torch.as_tensor(rank, device=self.device)
+        return self._tag_order, self._tag_rank_dev
+
+    def _box_dev(self):
+        """(lo, len) of the box as device addresses of the barostat record's words, (None, None) without a barostat: the kernels
+        then take the host's box"""
+        if self._npt is None:
+            return None, None
+        state = self._npt["state"]
+        return state[NPT_LAYOUT["lo"]].data_ptr(), state[NPT_LAYOUT["len"]].data_ptr()
+
+    def set_images(self, on: bool = True):
+        """LAMMPS' ``image`` flags: from this call on the wrap of every re-neighbouring (ani_md_wrap_positions_images,
+        include/ani_md_transport.h, in place of ani_md_wrap_positions -- the only place the loop wraps: step, run, minimize and the
+        rebuilds under the barostat) adds the box lengths it removes from an owned atom to an [nlocal, 3] int32 table, which starts
+        at zero: images count from this call.  Calling it again while the table exists changes nothing.  set_images(False) drops the
+        table: the loop launches what it launched before; raises while an MSD or a dump is set (they need the flags).  One rank
+        with native re-neighbouring only (the owned atoms keep their order there)."""
+        self._transport_guard("set_images")
+        if not on:
+            if self._msd is not None or self._dump is not None:
+                raise RuntimeError("VerletRun.set_images(False): an MSD or a dump is set, which read the image flags -- clear them "
+                                   "first (set_msd({}), set_dump(0))")
+            self._img = None
+        elif self._img is None:
+            self._img = torch.zeros((self.nlocal, 3), dtype=torch.int32, device=self.device)
+
+    def images(self) -> np.ndarray:
+        """the image flags [n, 3] int32 in ascending order of the global tag (``dump custom ... ix iy iz``)"""
+        if self._img is None:
+            raise RuntimeError("VerletRun.images: no image flags are kept (set_images)")
+        return self._img.cpu().numpy()[self._tag_rank()[0]]
+
+    def _unwrap_into(self, out):
+        self._check(self._md.ani_md_unwrap(self.x.data_ptr(), self._img.data_ptr(), self.nlocal, self._len3.ctypes.data,
+                                           self._box_dev()[1], self._pmask, out.data_ptr(), self._stream))
+
+    def unwrapped_positions(self) -> np.ndarray:
+        """x + image * len of the owned atoms (LAMMPS' ``xu``), [n, 3] fp64 in ascending order of the global tag, from ani_md_unwrap
+        with the box of the moment (under set_npt the barostat's device record)"""
+        if self._img is None:
+            raise RuntimeError("VerletRun.unwrapped_positions: no image flags are kept (set_images)")
+        out = torch.empty((self.nlocal, 3), dtype=torch.float64, device=self.device)
+        self._unwrap_into(out)
+        return out.cpu().numpy()[self._tag_rank()[0]]
+
+    def set_msd(self, groups, stride: int = 0, capacity: int = 4096):
+        """``compute msd`` (com no and com yes at once) for up to 8 groups against one stored origin (ani_md_msd_sample,
+        include/ani_md_transport.h), fp64 whatever the handle.  groups: an ordered dict name -> None (all atoms), a species symbol,
+        a list of symbols, or an array of global tags.  The host sorts the atoms into the distinct membership patterns (at most 16
+        classes), so overlapping groups cost one pass.  Turns the image flags on (set_images) and stores the unwrapped positions
+        of this moment as the origin; reset_msd_origin() stores them again.  msd() samples now.  stride > 0: every step with
+        step_no % stride == 0 writes a row, after its positions are final, into a device buffer of `capacity` rows (the host counts
+        and wraps; msd_series reads).  minimize() does not sample.  An empty dict clears the MSD: the loop launches what it
+        launched before (the image flags stay until set_images(False)).  One rank with native re-neighbouring only.  Raises
+        ValueError for more than 8 groups or 16 classes, an unknown species or tag, stride < 0 and capacity < 1."""
+        self._transport_guard("set_msd")
+        from . import ani_hip
+        if int(stride) < 0 or int(capacity) < 1:
+            raise ValueError("VerletRun.set_msd: stride >= 0 and capacity >= 1")
+        groups = dict(groups)
+        if not groups:
+            self._msd = None
+            return
+        if len(groups) > ani_hip.MSD_MAXGROUP:
+            raise ValueError(f"VerletRun.set_msd: {len(groups)} groups, at most {ani_hip.MSD_MAXGROUP}")
+        n = self.nlocal
+        symbols = self.ani.species_symbols()
+        species = self.species[:n].cpu().numpy()
+        tags = self.tag.cpu().numpy()
+        member = np.zeros((len(groups), n), dtype=bool)
+        for g, (name, spec) in enumerate(groups.items()):
+            if spec is None:
+                member[g] = True
+                continue
+            items = [spec] if isinstance(spec, str) else list(np.asarray(spec).reshape(-1).tolist())
+            if items and all(isinstance(it, str) for it in items):
+                for sym in items:
+                    if sym not in symbols:
+                        raise ValueError(f"VerletRun.set_msd: group {name!r}: unknown species {sym!r} (the model has {symbols})")
+                    member[g] |= species == symbols.index(sym)
+            else:
+                try:
+                    want = np.array([int(t) for t in items], dtype=np.int64)
+                except (TypeError, ValueError):
+                    raise ValueError(f"VerletRun.set_msd: group {name!r}: expected None, species symbols or global tags") from None
+                missing = np.setdiff1d(want, tags)
+                if missing.size:
+                    raise ValueError(f"VerletRun.set_msd: group {name!r}: unknown tag {int(missing[0])}")
+                member[g] = np.isin(tags, want)
+        cls, masks, nclass = ani_hip.msd_classes(member)
+        if nclass > ani_hip.MSD_MAXCLASS:
+            raise ValueError(f"VerletRun.set_msd: the groups overlap in {nclass} distinct ways, at most {ani_hip.MSD_MAXCLASS} classes")
+        nclass = max(nclass, 1)
+        mass = self.mass[:, 0].contiguous()
+        mass_np = mass.cpu().numpy()
+        count = np.array([(cls == c).sum() for c in range(nclass)], dtype=np.int32)
+        cmass = np.array([mass_np[cls == c].sum() for c in range(nclass)], dtype=np.float64)
+        dev, ng = self.device, len(groups)
+        self.set_images(True)
+        self._msd = dict(names=list(groups), ngroup=ng, nclass=nclass, cls=torch.as_tensor(cls, device=dev), mass=mass,
+                         class_count=torch.as_tensor(count, device=dev), class_mass=torch.as_tensor(cmass, device=dev),
+                         group_mask=torch.as_tensor(masks, device=dev),
+                         group_count=[int(sum(int(count[c]) for c in range(nclass) if (int(masks[g]) >> c) & 1)) for g in range(ng)],
+                         x0u=torch.empty((n, 3), dtype=torch.float64, device=dev),
+                         work=torch.empty(self._md.ani_md_msd_work_size(n, nclass), dtype=torch.float64, device=dev),
+                         out=torch.zeros((ng, ani_hip.MSD_NOUT), dtype=torch.float64, device=dev), stride=int(stride),
+                         capacity=int(capacity), nsamples=0,
+                         series=torch.zeros((int(capacity), 1 + ng * ani_hip.MSD_NOUT), dtype=torch.float64, device=dev) if stride else None)
+        self.reset_msd_origin()
+
+    def reset_msd_origin(self):
+        """the unwrapped positions of this moment become the origin of the MSD"""
+        if self._msd is None:
+            raise RuntimeError("VerletRun.reset_msd_origin: no MSD is set (set_msd)")
+        self._unwrap_into(self._msd["x0u"])
+
+    def _msd_sample(self, series_row):
+        ms = self._msd
+        self._check(self._md.ani_md_msd_sample(self.x.data_ptr(), self._img.data_ptr(), ms["x0u"].data_ptr(), ms["mass"].data_ptr(),
+                                               ms["cls"].data_ptr(), self.nlocal, ms["nclass"], ms["class_count"].data_ptr(),
+                                               ms["class_mass"].data_ptr(), ms["group_mask"].data_ptr(), ms["ngroup"],
+                                               self._len3.ctypes.data, self._box_dev()[1], self._pmask, ms["work"].data_ptr(),
+                                               ms["out"].data_ptr(), float(self.step_no), series_row, self._stream))
+
+    def msd(self) -> dict:
+        """sample now (no series row) and read: per group name a dict of msd [4] (x, y, z, total: com no), msd_com [4] (com yes),
+        dcm [3] (the displacement of the group's centre of mass), count and nonfinite (atoms whose displacement is not finite; their
+        NaN is in the sums).  One synchronising read."""
+        if self._msd is None:
+            raise RuntimeError("VerletRun.msd: no MSD is set (set_msd)")
+        from .ani_hip import msd_dict
+        self._msd_sample(None)
+        out = self._msd["out"].cpu().numpy()
+        return {name: msd_dict(out[g], self._msd["group_count"][g]) for g, name in enumerate(self._msd["names"])}
+
+    def msd_series(self, reset: bool = False) -> dict:
+        """The rows written so far, in time order: step [ns], groups: per group name a dict of msd [ns, 4], msd_com [ns, 4],
+        dcm [ns, 3] and nonfinite [ns]; rows [ns, ngroup, 12], the raw outputs; and dropped (rows overwritten because more than
+        `capacity` were written since the last reset).  One copy of the buffer; synchronises only here.  reset: start an empty
+        series afterwards."""
+        ms = self._msd
+        if ms is None:
+            raise RuntimeError("VerletRun.msd_series: no MSD is set (set_msd)")
+        from .ani_hip import MSD_LAYOUT, MSD_NOUT
+        ng, cap, ns = ms["ngroup"], ms["capacity"], ms["nsamples"]
+        if ms["series"] is None or ns == 0:
+            rows = np.zeros((0, 1 + ng * MSD_NOUT))
+        else:
+            buf = ms["series"].cpu().numpy()
+            rows = buf[:ns] if ns <= cap else np.concatenate([buf[ns % cap:], buf[: ns % cap]])
+        if reset:
+            ms["nsamples"] = 0
+        per = rows[:, 1:].reshape(-1, ng, MSD_NOUT).copy()
+        groups = {name: dict(msd=per[:, g, MSD_LAYOUT["msd"]], msd_com=per[:, g, MSD_LAYOUT["com"]], dcm=per[:, g, MSD_LAYOUT["dcm"]],
+                             nonfinite=per[:, g, MSD_LAYOUT["nonfinite"]]) for g, name in enumerate(ms["names"])}
+        return dict(step=rows[:, 0].astype(np.int64), groups=groups, rows=per, dropped=max(0, ns - cap))
+
+    def set_dump(self, every: int, path=None, unwrap: bool = False, capacity: int = 64):
+        """``dump dcd`` / ``dump custom``: every `every`-th step (step_no % every == 0), after its positions are final, one launch
+        (ani_md_frame_pack, include/ani_md_transport.h) packs the owned atoms in ascending order of their global tag as fp32,
+        with the box of the moment, into a device ring of `capacity` frames.  A full ring is drained with one device-to-host copy
+        and one synchronisation; frames() and close_dump() drain what is there.  path: the drained frames are appended to that
+        DCD file (dcd.DCDWriter); None: they are kept on the host for frames().  unwrap: write x + image * len instead of the
+        wrapped positions.  Turns the image flags on (set_images).  set_dump(0) closes the file and clears the dump: the loop
+        launches what it launched before.  minimize() writes no frame.  One rank with native re-neighbouring only.  Raises
+        ValueError for every < 0 and capacity < 1."""
+        self._transport_guard("set_dump")
+        if int(every) < 0 or int(capacity) < 1:
+            raise ValueError("VerletRun.set_dump: every >= 0 and capacity >= 1")
+        self.close_dump()
+        if int(every) == 0:
+            return
+        from .dcd import DCDWriter
+        n, every, capacity = self.nlocal, int(every), int(capacity)
+        self.set_images(True)
+        # a frame of the ring: the cell (six doubles), then the [3][n] fp32 block, padded to whole doubles -- one buffer, one copy
+        stride = 48 + (12 * n + 7) // 8 * 8
+        first = (self.step_no // every + 1) * every
+        self._dump = dict(every=every, unwrap=bool(unwrap), capacity=capacity, stride=stride, nring=0, steps=[], kept=[],
+                          ring=torch.zeros((capacity, stride), dtype=torch.uint8, device=self.device), row=self._tag_rank()[1],
+                          writer=None if path is None else DCDWriter(path, n, first, every, self.dt))
+
+    def _dump_frame(self):
+        dp, n = self._dump, self.nlocal
+        at = dp["ring"].data_ptr() + dp["nring"] * dp["stride"]
+        lo_dev, len_dev = self._box_dev()
+        self._check(self._md.ani_md_frame_pack(self.x.data_ptr(), self._img.data_ptr(), n, dp["row"].data_ptr(), self._lo3.ctypes.data,
+                                               self._len3.ctypes.data, lo_dev, len_dev, self._pmask, 1 if dp["unwrap"] else 0,
+                                               at + 48, at, self._stream))
+        dp["steps"].append(self.step_no)
+        dp["nring"] += 1
+        if dp["nring"] == dp["capacity"]:
+            self._drain_dump()
+
+    def _drain_dump(self):
+        """the frames of the ring to the host (one copy, which synchronises), then to the file or the kept list"""
+        dp, n = self._dump, self.nlocal
+        nf = dp["nring"]
+        if nf == 0:
+            return
+        buf = dp["ring"][:nf].cpu().numpy()
+        cell = np.ascontiguousarray(buf[:, :48]).view(np.float64)
+        xyz = np.ascontiguousarray(buf[:, 48:48 + 12 * n]).view(np.float32).reshape(nf, 3, n)
+        for k, step in enumerate(dp["steps"]):
+            if dp["writer"] is not None:
+                dp["writer"].append(cell[k], xyz[k])
+            else:
+                dp["kept"].append((step, cell[k].copy(), xyz[k].T.copy()))
+        dp["nring"], dp["steps"] = 0, []
+
+    def frames(self, reset: bool = True) -> dict:
+        """Drain the ring and return the frames kept on the host (a dump without a path; with a path they are in the file and this
+        returns none): step [nf], cell [nf, 6] (lo, then len, of the box at each frame) and xyz [nf, n, 3] fp32 in ascending order
+        of the global tag.  reset: forget them afterwards."""
+        dp = self._dump
+        if dp is None:
+            raise RuntimeError("VerletRun.frames: no dump is set (set_dump)")
+        self._drain_dump()
+        kept = dp["kept"]
+        out = dict(step=np.array([k[0] for k in kept], dtype=np.int64),
+                   cell=np.array([k[1] for k in kept], dtype=np.float64).reshape(-1, 6),
+                   xyz=np.array([k[2] for k in kept], dtype=np.float32).reshape(-1, self.nlocal, 3))
+        if reset:
+            dp["kept"] = []
+        return out
+
+    def close_dump(self):
+        """drain the ring, close the DCD file and clear the dump; returns what frames() would have returned (None when no dump was
+        set)"""
+        if self._dump is None:
+            return None
+        out = self.frames()
+        if self._dump["writer"] is not None:
+            self._dump["writer"].close()
+        self._dump = None
+        return out
 
     def _forces_overlapped(self):
         """Forward exchange, PairANI::compute and reverse exchange of a step that keeps its list, the two exchanges on the
