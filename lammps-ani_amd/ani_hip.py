@@ -182,6 +182,22 @@ def msd_dict(row, count: int) -> dict:
                 count=int(count), nonfinite=int(row[MSD_LAYOUT["nonfinite"]]))
 
 
+# include/ani_md_protocol.h: the centre-of-mass record (ANI_MD_COM_*) and the flags of ani_md_com_apply;
+# tests/test_protocol_reference_cpu.py holds the table against the header
+COM_NREC = 24
+COM_LAYOUT = dict(mass=0, xcm=slice(1, 4), vcm=slice(4, 7), angmom=slice(7, 10), inertia=slice(10, 16), omega=slice(16, 19), singular=19,
+                  nonfinite=20, count=21, zero=slice(22, 24))
+COM_FLAG_LINEAR, COM_FLAG_ANGULAR, COM_FLAG_RECENTER = 1, 2, 4
+
+
+def com_state_dict(rec) -> dict:
+    """the ANI_MD_COM_NREC doubles of a centre-of-mass record (host array) as a dict; inertia: xx yy zz xy xz yz"""
+    out = _record_dict(rec, COM_LAYOUT, 0)
+    for name in ("singular", "nonfinite", "count"):
+        out[name] = int(out[name])
+    return out
+
+
 def fire_params(dt0, etol, ftol, maxiter, **kw) -> FireParams:
     """ani_md_fire_params with the defaults of LAMMPS `min_modify` (dtmax = 10 dt0, dtmin = 0.02 dt0, ...); kw overrides them"""
     vals = dict(dt0=float(dt0), dtmax=10.0 * dt0, dtmin=0.02 * dt0, dtgrow=1.1, dtshrink=0.5, alpha0=0.25, alphashrink=0.99,
@@ -335,6 +351,12 @@ def lib():
                                         C.c_double, C.c_void_p, C.c_void_p]
         L.ani_md_frame_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        # include/ani_md_protocol.h: centre of mass, momentum, recentring
+        L.ani_md_com_work_size.argtypes = [C.c_int]
+        L.ani_md_com_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ani_md_com_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         # include/ani_comm.h
         L.ani_comm_get_unique_id.argtypes = [C.c_void_p]
         L.ani_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

@@ -11,24 +11,6 @@ static_assert(ANI_MD_MSD_MAXCLASS <= 32, "a group is a bit mask of classes in an
 
 constexpr int MSD_NSUM = 10;   // per class: S2[3], S1[3], Sm[3], non-finite atoms
 
-// the box of the moment: three doubles of the device record when there is one, the host's otherwise
-struct Box3 {
-  double len[3];
-};
-__device__ __forceinline__ Box3 box_now(double L0, double L1, double L2, const double* __restrict__ box_dev) {
-  Box3 b = {{L0, L1, L2}};
-  if (box_dev) { b.len[0] = box_dev[0]; b.len[1] = box_dev[1]; b.len[2] = box_dev[2]; }
-  return b;
-}
-
-// THE unwrapped coordinate (include/ani_md_transport.h): product and sum rounded separately, never contracted into an fma
-__device__ __forceinline__ double unwrapped(double x, int image, double L, int periodic) {
-#pragma clang fp contract(off)
-  if (!periodic) return x;
-  const double shift = (double)image * L;
-  return x + shift;
-}
-
 // wrap_kernel of ani_kernels_md.hip, the same expression and the same two clamps, with the box lengths it removed kept as counts
 __global__ __launch_bounds__(256) void wrap_images_kernel(double* __restrict__ x, int* __restrict__ image, int n, double lo0, double lo1,
                                                           double lo2, double l0, double l1, double l2, int pmask) {

@@ -1,6 +1,6 @@
 // ani_md_device.h — device pieces and launch helpers that the translation units of the timestep loop share (ani_kernels_md*.hip):
 // block reductions in a fixed order, the displacement fold, fix langevin's counter-based draws, the minimum image of one
-// component.  Everything is internal to the unit that includes it.
+// component, the box of the moment and the unwrapped coordinate.  Everything is internal to the unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,6 +73,25 @@ __device__ __forceinline__ long long through3(const long long* __restrict__ idx,
 }
 
 __device__ __forceinline__ double minimg1(double a, double L, int periodic) { return periodic ? a - L * rint(a / L) : a; }
+
+// the box of the moment: three doubles of the device record when there is one, the host's otherwise
+struct Box3 {
+  double len[3];
+};
+__device__ __forceinline__ Box3 box_now(double L0, double L1, double L2, const double* __restrict__ box_dev) {
+  Box3 b = {{L0, L1, L2}};
+  if (box_dev) { b.len[0] = box_dev[0]; b.len[1] = box_dev[1]; b.len[2] = box_dev[2]; }
+  return b;
+}
+
+// THE unwrapped coordinate (include/ani_md_transport.h; ani_md_protocol.h takes its centre of mass in it): product and sum rounded
+// separately, never contracted into an fma
+__device__ __forceinline__ double unwrapped(double x, int image, double L, int periodic) {
+#pragma clang fp contract(off)
+  if (!periodic) return x;
+  const double shift = (double)image * L;
+  return x + shift;
+}
 
 // ---- launches ---------------------------------------------------------------------------------------------------------------
 // everything goes on the caller's stream; blocks(count) workgroups of 256 threads unless an entry point says otherwise

@@ -101,7 +101,7 @@ class VerletRun:
     def __init__(self, ani, inp, box_len, device, dt: float = 0.5, cutoff: float = 5.1, skin: float = 2.0,
                  every: int = 10, masses=ANI2X_MASSES, group=None, seed: int = 12345,
                  langevin=None, box_lo=None, grid=None, periodic=(True, True, True), overlap=None, native_comm=None,
-                 force_collectives=False, vflag=False):
+                 force_collectives=False, vflag=False, atom_masses=None):
         """ani: ani_hip.ANI (full list, any precision); inp: harness.RankInput of this rank — only its OWNED atoms
         (positions, types, global tags) are taken, ghosts and lists are rebuilt here; langevin: None or
         (T_target, damp_fs) as ``fix langevin T T damp seed``; grid: processor grid (default comm.grid_for(world));
@@ -113,7 +113,10 @@ class VerletRun:
         native_comm: an ani_hip.NativeComm -- the exchanges then run inside libani_hip.so as grouped ncclSend / ncclRecv
         (include/ani_comm.h) instead of torch.distributed collectives; force_collectives: a single rank takes the several-rank
         paths (one-participant collectives), so that one GPU can exercise them.  vflag: every force evaluation also
-        accumulates the pair style's virial (``virial()``; LAMMPS sets vflag on thermo steps with a pressure compute)."""
+        accumulates the pair style's virial (``virial()``; LAMMPS sets vflag on thermo steps with a pressure compute).
+        atom_masses: [nlocal] g/mol in the order of inp's owned atoms (``fix property/atom rmass``, hydrogen mass repartitioning):
+        they take the place of the lookup by species wherever the loop uses a mass.  One rank with native re-neighbouring only (the
+        owned atoms keep their order there)."""
         if torch.device(device).type != "cuda":
             raise ValueError(f"VerletRun needs a HIP device (torch device type 'cuda'), got {device!r}: every step of the loop is one of "
                              "libani_hip's device entry points (include/ani_md.h, ani_build_list_device), which take device pointers")
@@ -133,6 +136,14 @@ class VerletRun:
         self.masses = torch.as_tensor(np.asarray(masses, dtype=np.float64), device=device)
         self.langevin = langevin
         n = inp.nlocal
+        self._atom_masses = None
+        if atom_masses is not None:
+            am = np.asarray(atom_masses, dtype=np.float64).reshape(-1)
+            if am.shape[0] != n or not (np.isfinite(am).all() and (am > 0.0).all()):
+                raise ValueError(f"VerletRun: atom_masses must be {n} positive finite masses (one per owned atom), got {am.shape[0]}")
+            if self.dc.multi:
+                raise RuntimeError("VerletRun: atom_masses: one rank only (the masses would have to migrate with their atoms)")
+            self._atom_masses = torch.as_tensor(am, device=device).contiguous()
         self.nlocal = n
         self.x = torch.as_tensor(inp.x[:n], dtype=torch.float64, device=device).contiguous()
         self.species = torch.as_tensor(inp.species[:n].astype(np.int32), device=device)
@@ -164,6 +175,8 @@ class VerletRun:
         # one rank: re-neighbouring (position wrap, ghost shell, buffers, displacement check) through the kernels of
         # include/ani_md.h instead of tensor operations; ANI_MD_NATIVE_REBUILD=0 keeps the tensor forms (measurements, tests)
         self._native_rebuild = bool(not self.dc.multi and os.environ.get("ANI_MD_NATIVE_REBUILD", "1") not in ("", "0"))
+        if self._atom_masses is not None and not self._native_rebuild:
+            raise RuntimeError("VerletRun: atom_masses needs the device loop with native re-neighbouring (one rank on the GPU)")
         self._cap = 0
         self._cons = None      # bond constraints (set_constraints): None, or the device tables and parameters of the two stages
         self._ncons = 0        # constrained bonds: degrees of freedom that temperature() does not count
@@ -174,6 +187,9 @@ class VerletRun:
         self._img = None       # image flags (set_images): None, or the [nlocal, 3] int32 table that the wrap keeps
         self._msd = None       # mean-squared displacements (set_msd): None, or the classes, the origin, scratch, outputs and series
         self._dump = None      # trajectory frames (set_dump): None, or the device ring, its host side and the DCD writer
+        self._com = None       # centre-of-mass record, scratch and host words (com_state, zero_momentum, ...), made at first use
+        self._mom = None       # fix momentum (set_momentum): None, or every and the flags of ani_md_com_apply
+        self._recenter = None  # fix recenter (set_recenter): None, or the fractions and the dimension mask
         self._tag_order = None  # the owned atoms in ascending order of their global tag (_tag_rank), made at first use
         self._thermo_buf = None
         if self._overlap:
@@ -211,7 +227,8 @@ class VerletRun:
         if not self.dc.multi and getattr(self, "_factors_n", -1) == n:
             return   # one rank: nobody migrates, the owned atoms keep their order
         self._factors_n = n
-        m = self.masses[self.species[:n].long()]
+        am = getattr(self, "_atom_masses", None)
+        m = self.masses[self.species[:n].long()] if am is None else am
         self.mass = m[:, None]
         self._dtfm1 = (0.5 * self.dt * FTM2V) / m                        # [n], the kernels' form
         self._g1 = self._g2 = None
@@ -374,8 +391,12 @@ class VerletRun:
             fl.addcmul_(g1, self.v)
             fl.addcmul_(g2, r)
 
-    def create_velocities(self, T: float):
-        """``velocity all create T seed mom yes dist gaussian`` (examples/benchmark/in.lammps:54)."""
+    def create_velocities(self, T: float, rot: bool = False):
+        """``velocity all create T seed mom yes dist gaussian`` (examples/benchmark/in.lammps:54).  rot: ``rot yes`` as well -- the
+        angular momentum about the centre of mass is taken out (zero_momentum) before the rescale."""
+        if rot:
+            self._protocol_guard("create_velocities(rot=True)")
+            self._need_images("create_velocities(rot=True)")
         if T <= 0.0:
             self.v.zero_()
             return
@@ -390,6 +411,8 @@ class VerletRun:
             pm = pm.to(self.device)
             p, mtot = pm[:3], pm[3:]
         self.v -= p / mtot
+        if rot:
+            self.zero_momentum(linear=False, angular=True)
         if self._cons is not None:
             self.project_velocities()   # the components along the constrained bonds carry no temperature: out before the rescale
         ke = self.kinetic_energy()
@@ -423,6 +446,8 @@ class VerletRun:
                                                           self._d2max.data_ptr(), self._stream))
         if self._cons is not None:
             self._shake_positions()
+        if self._recenter is not None:
+            self._recenter_now()
 
     def _middle(self, force_rebuild: bool = False):
         """between the two integrator halves: re-neighbouring decision, ghost positions, forces, ghost forces"""
@@ -478,33 +503,46 @@ class VerletRun:
                p_from=None, p_to=None):
         """nsteps steps of first half, middle, second half; with a thermostat the target goes from t_from (exclusive) to t_to (at
         the last step), and the call begins with the sum of the velocities as they are.  The one exception to the three pieces:
-        where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints --
-        the two are ONE launch, which carries the number of the step that ends."""
-        nvt = self._nvt
+        where nothing stands between the second half of a step and the first half of the next -- no thermostat, no constraints, no
+        fix momentum on that step -- the two are ONE launch, which carries the number of the step that ends."""
+        nvt, mom = self._nvt, self._mom
         one_launch = nvt is None and self._cons is None
         t = p = None
         if nvt is not None:
             self._nvt_kinetic()
+        fresh = nvt is not None      # the chain's next half-step sums the scratch; otherwise it goes on from the sum it scaled itself
+        moved = False                # the first half of this step ran in the launch that ended the last one
         for k in range(nsteps):
             if nvt is not None:
                 t = t_to if k + 1 == nsteps else t_from + ((k + 1) / nsteps) * (t_to - t_from)
             if p_to is not None:
                 p = p_to if k + 1 == nsteps else p_from + ((k + 1) / nsteps) * (p_to - p_from)
-            if k == 0 or not one_launch:
-                self._first_half(t, nvt["npart"] if nvt is not None and k == 0 else 0, p)   # later steps: the sum the chain scaled itself
+            if not moved:
+                self._first_half(t, nvt["npart"] if fresh else 0, p)
+                fresh = False
             if before_forces is not None:
                 before_forces(k)
             self._middle(force_rebuild)
             if after_forces is not None:
                 after_forces(k)
-            if one_launch and k + 1 < nsteps:
-                lang = self._g1 is not None
+            mom_now = mom is not None and self.step_no % mom["every"] == 0
+            moved = one_launch and k + 1 < nsteps and not mom_now
+            if moved:
+                lgv = self._g1 is not None
                 self._check(self._md.ani_md_final_initial_integrate(
                     self.x.data_ptr(), self.v.data_ptr(), self.f.data_ptr(), self._dtfm1.data_ptr(), self.dt, self.nlocal,
-                    1 if lang else 0, self._g1.data_ptr() if lang else None, self._g2.data_ptr() if lang else None,
+                    1 if lgv else 0, self._g1.data_ptr() if lgv else None, self._g2.data_ptr() if lgv else None,
                     self.tag.data_ptr(), self._seed, self.step_no, self.x_built.data_ptr(), self._d2max.data_ptr(), self._stream))
             else:
                 self._second_half(t, p)
+            if moved and self._recenter is not None:
+                self._recenter_now()         # behind the first half that the launch above held
+            if mom_now:                      # fix momentum end_of_step: on the full-step velocities
+                self._com_sample()
+                self._com_apply(mom["flags"])
+                if nvt is not None:          # the chain goes on from the sum of the velocities as they are now
+                    self._nvt_kinetic()
+                    fresh = True
 
     def step(self, force_rebuild: bool = False):
         """force_rebuild: re-neighbour in this step whatever the displacement check would say (measurements).  With a thermostat
@@ -809,6 +847,9 @@ class VerletRun:
             raise RuntimeError("VerletRun.set_npt needs vflag=True (the barostat reads the pair virial of every force evaluation)")
         if self.langevin is not None:
             raise RuntimeError("VerletRun.set_npt: the run has a Langevin thermostat (langevin=...); one temperature control at a time")
+        if self._recenter is not None:
+            raise RuntimeError("VerletRun.set_npt: recentring is set (set_recenter): its target is a fraction of a box at rest -- clear "
+                               "it with set_recenter(None) first")
         if self.dc.multi:
             raise RuntimeError("VerletRun.set_npt: one rank only (kinetic energy and virial are not reduced over ranks)")
         if not self._native_rebuild:
@@ -1120,6 +1161,112 @@ class VerletRun:
             rs["nsamples"] = 0
         return dict(step=rows[:, 0].astype(np.int64), cv=rows[:, 1:1 + nr].copy(), ebias=rows[:, 1 + nr:].copy(), dropped=max(0, ns - cap))
 
+    # ---- centre of mass, momentum, recentring (include/ani_md_protocol.h) -----------------------------------------------------
+    def _protocol_guard(self, who: str):
+        if self.dc.multi:
+            raise RuntimeError(f"VerletRun.{who}: one rank only (the sums are not reduced over ranks)")
+        if not self._native_rebuild:
+            raise RuntimeError(f"VerletRun.{who} needs the device loop with native re-neighbouring (one rank on the GPU)")
+
+    def _need_images(self, who: str):
+        if self._img is None and any(self.dc.periodic):
+            raise RuntimeError(f"VerletRun.{who}: a dimension is periodic, and the centre of mass is taken in unwrapped coordinates -- "
+                               "call set_images() first")
+
+    def _com_buffers(self):
+        if self._com is None:
+            from . import ani_hip
+            n = self.nlocal
+            self._com = dict(mass=self.mass[:, 0].contiguous(), ref=np.zeros(3), target=np.zeros(3),
+                             work=torch.empty(self._md.ani_md_com_work_size(n), dtype=torch.float64, device=self.device),
+                             rec=torch.zeros(ani_hip.COM_NREC, dtype=torch.float64, device=self.device))
+        return self._com
+
+    def _com_sample(self):
+        """the record of ani_md_com_sample for the owned atoms as they are, the raw moments taken about the box centre"""
+        c = self._com_buffers()
+        c["ref"][:] = self._box_lo_np + 0.5 * self._box_len_np
+        self._check(self._md.ani_md_com_sample(self.x.data_ptr(), None if self._img is None else self._img.data_ptr(), self.v.data_ptr(),
+                                               c["mass"].data_ptr(), self.nlocal, c["ref"].ctypes.data, self._len3.ctypes.data,
+                                               self._box_dev()[1], self._pmask, c["work"].data_ptr(), c["rec"].data_ptr(), self._stream))
+
+    def _com_apply(self, flags: int, dim_mask: int = 0):
+        c = self._com
+        self._check(self._md.ani_md_com_apply(self.x.data_ptr(), self.v.data_ptr(), None if self._img is None else self._img.data_ptr(),
+                                              self.nlocal, c["rec"].data_ptr(), flags, c["target"].ctypes.data, dim_mask,
+                                              self._len3.ctypes.data, self._box_dev()[1], self._pmask, self.x_built.data_ptr(),
+                                              self._d2max.data_ptr(), self._stream))
+
+    def com_state(self) -> dict:
+        """Sample now and read (one synchronising read): mass (g/mol), xcm [3] (unwrapped with image flags kept, else of the
+        positions as the loop holds them), vcm [3] (A/fs), angmom [3] about xcm (g/mol A^2/fs), inertia [6] about xcm (xx yy zz xy
+        xz yz, g/mol A^2), omega [3] (1/fs), singular (1: the inertia tensor has no inverse -- one atom, collinear atoms -- and omega
+        is zero), nonfinite (atoms with a non-finite position or velocity) and count."""
+        self._protocol_guard("com_state")
+        from .ani_hip import com_state_dict
+        self._com_sample()
+        return com_state_dict(self._com["rec"].cpu().numpy())
+
+    def zero_momentum(self, linear: bool = True, angular: bool = False):
+        """``velocity all zero linear`` / ``zero angular``, one pass of ``fix momentum``: one sample and one apply
+        (ani_md_com_sample / ani_md_com_apply), nothing read by the host.  angular needs the image flags (set_images) when a
+        dimension is periodic."""
+        self._protocol_guard("zero_momentum")
+        if angular:
+            self._need_images("zero_momentum(angular=True)")
+        flags = (1 if linear else 0) | (2 if angular else 0)
+        if flags:
+            self._com_sample()
+            self._com_apply(flags)
+
+    def set_momentum(self, every: int, linear: bool = True, angular: bool = False):
+        """``fix momentum every linear 1 1 1 [angular]``: at the end of every step with step_no % every == 0 the linear and / or
+        angular momentum of the owned atoms is taken out of the full-step velocities (one sample, one apply).  Those steps take the
+        separate second half, as step() does; the others keep the one-launch step boundary.  0 clears it: the loop launches what it
+        launched before.  angular needs the image flags (set_images) when a dimension is periodic."""
+        if int(every) < 0:
+            raise ValueError("VerletRun.set_momentum: every >= 0")
+        if int(every) == 0:
+            self._mom = None
+            return
+        self._protocol_guard("set_momentum")
+        if angular:
+            self._need_images("set_momentum(angular=True)")
+        flags = (1 if linear else 0) | (2 if angular else 0)
+        if not flags:
+            raise ValueError("VerletRun.set_momentum: linear, angular or both")
+        self._com_buffers()
+        self._mom = dict(every=int(every), flags=flags)
+
+    def set_recenter(self, fraction):
+        """``fix recenter fx fy fz units fraction``: (fx, fy, fz), None for a dimension that is left alone (LAMMPS' NULL).  Behind the
+        first half of every step, and behind the position stage of the constraints, one sample and one apply shift every owned atom
+        so that the centre of mass (unwrapped) stands at lo + f len; the shift counts in the displacement check.  None or False
+        clears it: the loop launches what it launched before.  Needs the image flags (set_images) when a dimension is periodic;
+        raises under set_npt (the target would be a fraction of a moving box)."""
+        if fraction is None or fraction is False:
+            self._recenter = None
+            return
+        self._protocol_guard("set_recenter")
+        if self._npt is not None:
+            raise RuntimeError("VerletRun.set_recenter: a barostat is set (set_npt): the target is a fraction of a box at rest")
+        try:
+            frac = [None if f is None else float(f) for f in fraction]
+        except (TypeError, ValueError):
+            raise ValueError("VerletRun.set_recenter: expected (fx, fy, fz) with None for a dimension that is left alone") from None
+        if len(frac) != 3 or not all(f is None or np.isfinite(f) for f in frac):
+            raise ValueError("VerletRun.set_recenter: expected three finite fractions (None for a dimension that is left alone)")
+        self._need_images("set_recenter")
+        self._com_buffers()
+        self._recenter = dict(frac=frac, dim_mask=sum(1 << k for k in range(3) if frac[k] is not None))
+
+    def _recenter_now(self):
+        rc, c = self._recenter, self._com
+        for k in range(3):
+            c["target"][k] = 0.0 if rc["frac"][k] is None else self._box_lo_np[k] + rc["frac"][k] * self._box_len_np[k]
+        self._com_sample()
+        self._com_apply(4, rc["dim_mask"])
+
     # ---- image flags, mean-squared displacements, trajectory frames ---------------------------------------------
     def _transport_guard(self, who: str):
         if self.dc.multi:
@@ -1157,6 +1304,9 @@ class VerletRun:
             if self._msd is not None or self._dump is not None:
                 raise RuntimeError("VerletRun.set_images(False): an MSD or a dump is set, which read the image flags -- clear them "
                                    "first (set_msd({}), set_dump(0))")
+            if self._recenter is not None or (self._mom is not None and self._mom["flags"] & 2):
+                raise RuntimeError("VerletRun.set_images(False): recentring or an angular fix momentum is set, which take the centre "
+                                   "of mass in unwrapped coordinates -- clear them first (set_recenter(None), set_momentum(0))")
             self._img = None
         elif self._img is None:
             self._img = torch.zeros((self.nlocal, 3), dtype=torch.int32, device=self.device)
